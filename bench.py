@@ -47,6 +47,23 @@ BASELINE configs 2 and 3 run in the same command:
   a ``dist.new_group``), every shard checked bitwise against hashes of the
   N-rank shards it was cut from.
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) does only what the
+headline needs: build the model, warm up, time the K takes, print the result
+line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` and the per-rank take times).  Everything described above
+and below besides the timed takes -- async takes, restores, raw blobs, fresh
+directories, the reference's DDP config, DDP Llama, elastic and HSDP
+restores, the per-rank phase capture -- runs only with ``--full``; the
+options that size those phases are ignored without it.
+
+``--dump-outputs DIR`` writes what the last timed take produced: right after
+the timed steps every local shard is zeroed and restored from the snapshot
+just written, and each parameter is saved as ``DIR/<name>.npy`` (float32;
+whole when small, else a fixed seeded sample of its elements, about 40 MB in
+all for Llama-3-8B).  The weights are seeded, so two builds given the same
+arguments can be compared file by file.  Ranks above 0 write
+``<name>.rank<r>.npy``.
+
 Launch: ``python bench.py --gpus N`` starts N ranks itself (one process per
 GPU, the parent never touches the GPU) and forwards rank 0's JSON line; a
 failing or hung rank fails the whole run.  Under torchrun
@@ -221,6 +238,40 @@ def _hsdp_phase(cfg, dev, gpu_index, world, rank, reps, root, opts, args, total_
     return out
 
 
+DUMP_SAMPLE = 32768  # elements kept of a tensor larger than this
+DUMP_SEED = 20240531
+
+
+def _dump_outputs(out_dir: str, path: str, model, app_state, rank: int) -> None:
+    """Write what the take at ``path`` stored: zero every local shard, restore
+    the snapshot into it, and save each parameter (or a fixed seeded sample of
+    a large one) as float32 ``<name>.npy``.  The model holds the same bytes
+    afterwards iff the take and the restore are correct."""
+    import numpy as np
+    import torch
+
+    from hipsnapshot import Snapshot
+
+    os.makedirs(out_dir, exist_ok=True)
+    for p in model.parameters():
+        p._local_tensor.zero_()
+    torch.cuda.synchronize()
+    Snapshot(path).restore(app_state)
+    torch.cuda.synchronize()
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    total = 0
+    for name, p in model.named_parameters():
+        flat = p._local_tensor.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=gen)
+            flat = flat[idx.to(flat.device)]
+        arr = flat.to(torch.float32).cpu().numpy()
+        total += arr.nbytes
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def _selftest_hook(rank: int) -> None:
     """``HSBENCH_SELFTEST`` (launcher tests on CPU, before any
     torch import): ``ok`` -- rank 0 prints a JSON line, every rank exits 0;
@@ -356,7 +407,24 @@ def main() -> None:
     ap.add_argument("--no-plan-gc", action="store_true",
                     help="A/B probe: skip the full GC pass after a take that built a plan "
                          "(knobs.TUNING.gc_after_plan)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other phase (async takes, "
+                         "restores, raw blobs, fresh directories, the reference's DDP config, "
+                         "DDP Llama, elastic and HSDP restores, per-rank phase capture); "
+                         "without it only the headline is measured and the options that size "
+                         "those phases are ignored")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, restore the snapshot the last step wrote and "
+                         "save every parameter (large ones as a fixed seeded sample) as "
+                         "DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.async_warmup = args.async_iters = 0
+        args.no_restore_check = True
+        args.raw_steps = args.fresh_steps = args.ddp_steps = args.ddp_llama_steps = 0
+        args.elastic_iters = args.hsdp = 0
 
     torchrun = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not torchrun and args.gpus > 1:
@@ -468,13 +536,17 @@ def main() -> None:
     dist.all_gather_object(per_rank, (statistics.mean(my_step_s) * 1e3, my_stored))
     rank_take_ms = sorted(r[0] for r in per_rank)
     rank_stored = [r[1] for r in per_rank]
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, path, model, app_state, rank)
     # one more (untimed) take with its phases captured on every rank: what a
     # multi-GPU curve needs to be attributed without another run
     from hipsnapshot.utils import rank_diag
 
-    barrier_sync()
-    my_diag = rank_diag.measure(lambda: Snapshot.take(path, app_state, storage_options=opts,
-                                                      compression=args.compression))
+    my_diag = {}
+    if args.full:
+        barrier_sync()
+        my_diag = rank_diag.measure(lambda: Snapshot.take(path, app_state, storage_options=opts,
+                                                          compression=args.compression))
     my_diag["numa"] = numa_rep
 
     # async_take: time-to-unblock
@@ -859,6 +931,14 @@ def main() -> None:
                              "median": round(statistics.median(rank_take_ms), 2),
                              "min": round(rank_take_ms[0], 2)},
             "rank_stored_bytes": rank_stored,
+            "compression": args.compression,
+            "stored_bytes": stored,
+            # rank 0's Python cyclic-GC time inside the timed takes
+            "gc_ms_in_timed_takes": round(gc_take_ms, 2),
+            "full": args.full,
+        }
+        # what --full measured after the timed steps
+        extra = {
             # median over the async iterations (each value listed below)
             "time_to_unblock_ms": round(statistics.median(unblock), 2) if unblock else None,
             "time_to_unblock_ms_each": [round(u, 2) for u in unblock],
@@ -878,10 +958,7 @@ def main() -> None:
             "restore_bitwise_ok": restore_ok,
             "restore_GBps": round(restore_gbps, 2) if restore_gbps else None,
             "restore_GBps_each": restore_each, **restore_info,
-            "compression": args.compression,
-            "stored_bytes": stored,
-            # rank 0's Python cyclic-GC time inside the timed takes / restores
-            "gc_ms_in_timed_takes": round(gc_take_ms, 2),
+            # rank 0's Python cyclic-GC time inside the timed restores
             "gc_ms_in_timed_restores": round(gc_restore_ms, 2) if gc_restore_ms is not None
             else None,
             "raw_GBps": round(raw_gbps, 3) if raw_gbps else None,
@@ -910,9 +987,11 @@ def main() -> None:
             "memory_held_after_restore": held_after_restore,
             # one untimed take per rank with its phases captured
             # (utils/rank_diag.py), and the one-line skew summary
-            "rank_skew": rank_diag.skew(all_diag),
+            "rank_skew": rank_diag.skew(all_diag) if args.full else None,
             "rank_diag": all_diag,
         }
+        if args.full:
+            out.update(extra)
         print(json.dumps(out), flush=True)
     dist.barrier()
     if rank == 0:

@@ -1,6 +1,6 @@
 """Restore in a FRESH process (the restart-after-failure case).
 
-``bench.py`` times restores in the process that just saved: the pinned host
+``bench.py --full`` times restores in the process that just saved: the pinned host
 pool, the device caching allocator and the HIP code objects are all warm.
 A job restarting from a checkpoint has none of that.  This benchmark saves
 the Llama-3-8B FSDP state in one process, then restores it in a second,

@@ -18,7 +18,7 @@ run() {
     tail -1 $R/$tag.json | cut -c1-700
   done
 }
-run bench python bench.py --steps 5 --warmup 2
+run bench python bench.py --full --steps 5 --warmup 2
 run ddp_20gb python benchmarks/ddp/main.py --repeats 3
 run fsdp python benchmarks/fsdp/main.py
 run load_tensor python benchmarks/load_tensor/main.py

@@ -10,7 +10,7 @@ mkdir -p $O
 export PYTHONUNBUFFERED=1 HSBENCH_DIR=$PWD/bench_tmp
 mkdir -p $HSBENCH_DIR
 N=${N:-8}
-timeout -k 10 1000 python bench.py --gpus $N --backend gloo --steps 2 --warmup 1 \
+timeout -k 10 1000 python bench.py --gpus $N --full --backend gloo --steps 2 --warmup 1 \
     --async-iters 2 --restore-iters 2 --raw-steps 1 --fresh-steps 0 --ddp-steps 0 \
     --ddp-llama-layers ${DDP_LAYERS:-4} --no-numa-bind ${ARGS:-} \
     > $O/reh${N}.json 2> $O/reh${N}.err \

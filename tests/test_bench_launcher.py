@@ -59,7 +59,7 @@ def test_torchrun_world_size_mismatch_is_an_error():
 def test_self_launched_two_rank_bench_on_one_gpu(tmp_path):
     """Two gloo ranks sharing the GPU, launched by bench.py itself, with the
     DDP (config 2) and elastic 2 -> 1 (config 3) phases, all bitwise."""
-    p, _ = _run(["--gpus", "2", "--backend", "gloo", "--model", "tiny", "--steps", "2",
+    p, _ = _run(["--gpus", "2", "--full", "--backend", "gloo", "--model", "tiny", "--steps", "2",
                  "--warmup", "1", "--async-iters", "1", "--restore-iters", "1",
                  "--raw-steps", "1", "--fresh-steps", "0", "--ddp-steps", "0",
                  "--no-numa-bind", "--path", str(tmp_path / "b")], {}, timeout=600)
@@ -71,3 +71,28 @@ def test_self_launched_two_rank_bench_on_one_gpu(tmp_path):
     assert len(out["ddp_llama_rank_written_bytes"]) == 2
     assert out["elastic_bitwise_ok"] is True and out["elastic_to_ranks"] == 1
     assert out["vs_baseline"] is None  # no reference number at 2 GPUs
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_take(tmp_path):
+    """Without --full only the timed takes run (the phase options are
+    ignored); --dump-outputs writes the restored snapshot as float32 .npy."""
+    import numpy as np
+
+    dump = tmp_path / "dump"
+    p, _ = _run(["--gpus", "1", "--backend", "gloo", "--model", "tiny", "--steps", "2",
+                 "--warmup", "1", "--raw-steps", "1", "--no-numa-bind",
+                 "--path", str(tmp_path / "b"), "--dump-outputs", str(dump)], {}, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["full"] is False
+    assert out["unit"] == "GB/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    for key in ("restore_GBps", "raw_GBps", "time_to_unblock_ms", "ddp_llama_GBps", "rank_diag"):
+        assert key not in out, key
+    files = sorted(dump.glob("*.npy"))
+    assert files and not (tmp_path / "b").exists()
+    arrays = [np.load(f) for f in files]
+    assert all(a.dtype == np.float32 and a.ndim == 1 for a in arrays)
+    assert sum(a.nbytes for a in arrays) <= 64 << 20
+    assert all(np.isfinite(a).all() for a in arrays)
+    assert sum(int(np.count_nonzero(a)) for a in arrays) > 0.9 * sum(a.size for a in arrays)
