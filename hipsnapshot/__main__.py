@@ -7,6 +7,11 @@
         the same, each rank checking 1/N of the blobs
     python -m hipsnapshot info PATH
         print the snapshot's version, world size and entry counts
+    python -m hipsnapshot deps PATH
+        print the snapshot directories an incremental snapshot points into
+    python -m hipsnapshot materialize PATH
+        link (or copy) every blob PATH references in a base into PATH, so the
+        bases can be deleted
 """
 
 from __future__ import annotations
@@ -59,6 +64,24 @@ def _info(args) -> int:
     return 0
 
 
+def _deps(args) -> int:
+    from .snapshot import Snapshot
+
+    for d in Snapshot(args.path).dependencies():
+        print(d)
+    return 0
+
+
+def _materialize(args) -> int:
+    from .snapshot import Snapshot
+
+    snap = Snapshot(args.path)
+    deps = snap.dependencies()
+    snap.materialize()
+    print(f"{args.path}: self-contained (was pointing into {len(deps)} snapshot(s))")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m hipsnapshot")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -72,6 +95,12 @@ def main(argv=None) -> int:
     i = sub.add_parser("info", help="summarise a snapshot's metadata")
     i.add_argument("path")
     i.set_defaults(fn=_info)
+    d = sub.add_parser("deps", help="list the snapshots an incremental snapshot points into")
+    d.add_argument("path")
+    d.set_defaults(fn=_deps)
+    m = sub.add_parser("materialize", help="make an incremental snapshot self-contained")
+    m.add_argument("path")
+    m.set_defaults(fn=_materialize)
     args = ap.parse_args(argv)
     return args.fn(args)
 

@@ -220,6 +220,10 @@ class _Tuning:
     hash_grid = 64
     gpu_slab_gather = True
     slab_align = 256
+    # every take records per-leaf content digests (incremental takes' bases).
+    # Off: a take then runs no extra launch and writes no extra file; a job
+    # that checkpoints incrementally passes content_digests=True / base=
+    content_digests = False
     gc_after_plan = True       # one full GC pass after a take that built a plan
     plan_cache = True          # reuse a take's plan (engine/plan_cache.py)
     # async takes drain the frozen device state raw: the encoder on the CUs
@@ -350,6 +354,14 @@ def checksum_enabled() -> bool:
     (``.snapshot_checksums/<rank>``, ops/checksum.py); ``Snapshot.verify``
     and ``restore(verify=True)`` check them."""
     return _get_bool("CHECKSUM", True)
+
+
+def content_digests_enabled() -> bool:
+    """Default of ``Snapshot.take(content_digests=...)``: record the hs64 of
+    each eligible leaf's raw bytes in ``.snapshot_content/<rank>``
+    (engine/incremental.py), which makes every snapshot a full-value base for
+    ``take(base=...)``.  ``base=`` forces it on."""
+    return bool(_tuned("content_digests"))
 
 
 def get_hash_grid() -> int:

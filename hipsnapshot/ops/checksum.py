@@ -14,7 +14,7 @@ verify PATH`` re-reads every blob and checks it.
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import List, Optional
 
 import numpy as np
 
@@ -106,6 +106,34 @@ def device_hash_result(dev: int, slot: int, handle: int, nbytes: int) -> int:
                                                              ctypes.byref(out)),
                   "hsg_hash64_result")
     return finish(out.value, nbytes)
+
+
+def device_hash_batch(dev: int, blobs, stream: Optional[int] = None) -> List[int]:
+    """hs64 of every device blob ``(ptr, nbytes)`` of ``blobs`` on device
+    ``dev``: ONE ``hs_hash64_batch`` launch on ``stream`` (default: torch's
+    current stream of the device, so the hashes are ordered after whatever
+    produced the bytes) and one wait for all the sums."""
+    import ctypes
+
+    from . import native
+
+    n = len(blobs)
+    if n == 0:
+        return []
+    lib = native.require_gpu_lib()
+    if stream is None:
+        import torch
+
+        stream = int(torch.cuda.current_stream(dev).cuda_stream)
+    descs = np.empty((n, 2), dtype=np.uint64)
+    for i, (ptr, nbytes) in enumerate(blobs):
+        descs[i, 0] = ptr if nbytes else 0
+        descs[i, 1] = nbytes
+    sums = np.zeros(n, dtype=np.uint64)
+    native._check(lib.hsg_hash64_batch(dev, stream or None, descs.ctypes.data, n,
+                                       sums.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+                  "hsg_hash64_batch")
+    return [finish(int(s), int(nb)) for s, (_, nb) in zip(sums, blobs)]
 
 
 def rank_file(rank: int) -> str:

@@ -315,6 +315,8 @@ def _load_hsgpu() -> Optional[ctypes.CDLL]:
         _declare(lib, "hsg_hash64", c_int, [c_int, c_int, c_int, c_void_p, c_uint64, c_uint64,
                                              c_int, ctypes.POINTER(c_int)])
         _declare(lib, "hsg_hash64_result", c_int, [c_int, c_int, c_int, ctypes.POINTER(c_uint64)])
+        _declare(lib, "hsg_hash64_batch", c_int,
+                 [c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_uint64)])
         _declare(lib, "hsg_sdma_last_error", c_char_p, [])
         _declare(lib, "hsg_sdma_engines", c_int, [c_int])
         _declare(lib, "hsg_sdma_h2d", c_int, [c_int, c_void_p, c_void_p, c_uint64])

@@ -86,6 +86,7 @@ from .parallel.partitioner import (
 )
 from .parallel.store import LinearBarrier, existing_store, get_or_create_store
 from .stateful import AppState, RNGState, Stateful
+from .storage.fs import FSStoragePlugin as _FSStoragePlugin
 from .storage.registry import url_to_storage_plugin_in_event_loop
 from .utils.tracing import paused_gc, roctx_range, timeline
 from .version import __version__
@@ -377,7 +378,9 @@ class Snapshot:
              storage_options: Optional[Dict[str, Any]] = None,
              _custom_tensor_prepare_func: Optional[PrepareFunc] = None,
              quantize: Optional[List[str]] = None,
-             compression: Optional[str] = None) -> "Snapshot":
+             compression: Optional[str] = None,
+             base: Optional[Any] = None,
+             content_digests: Optional[bool] = None) -> "Snapshot":
         """Take a snapshot of ``app_state`` at ``path`` (blocking).
 
         ``quantize``: optional glob patterns of logical paths whose floating
@@ -385,43 +388,81 @@ class Snapshot:
         ``compression``: ``"hsz1"`` stores GPU-resident floating-point blobs
         losslessly compressed (encoded on the GPU before D2H, ~0.67x for
         bf16, ~0.84x for fp32); default from ``HIPSNAPSHOT_COMPRESSION`` ("none").
+        ``base``: a committed snapshot (``Snapshot`` or path) on the same
+        local file system: eligible leaves whose content digest equals the
+        base's are not written, their entries point into the base
+        (engine/incremental.py; see ``dependencies`` / ``materialize``).
+        ``content_digests``: record each eligible leaf's hs64 in
+        ``.snapshot_content/<rank>`` so this snapshot is a full-value base
+        later (default ``knobs.TUNING.content_digests``, off; forced on by
+        ``base``).
         """
         torch._C._log_api_usage_once("hipsnapshot.Snapshot.take")
+        base_root = None
+        if base is not None:
+            from .engine.incremental import resolve_base
+
+            base_root = resolve_base(base, path)  # ValueError before anything is written
+            content_digests = True
+        elif content_digests is None:
+            content_digests = knobs.content_digests_enabled()
         memory.op_begin(pg)
         try:
             with paused_gc(plan_gc=False):
                 return cls._take(path, app_state, pg, replicated, storage_options,
-                                 _custom_tensor_prepare_func, quantize, compression)
+                                 _custom_tensor_prepare_func, quantize, compression,
+                                 base_root, bool(content_digests))
         finally:
             memory.op_end()
 
     @classmethod
     def _take(cls, path, app_state, pg, replicated, storage_options,
-              _custom_tensor_prepare_func, quantize, compression) -> "Snapshot":
+              _custom_tensor_prepare_func, quantize, compression,
+              base_root=None, content_digests=False) -> "Snapshot":
         cls._validate_app_state(app_state)
         _numa_bind_once()
         loop = asyncio.new_event_loop()
         comm = Comm(pg)
         t0 = time.monotonic()
         path, rep, keys, nonce, storage = cls._open_and_coalesce(
-            path, comm, app_state, replicated, loop, storage_options)
+            path, comm, app_state, replicated, loop, storage_options,
+            incremental=(base_root,) if content_digests else None)
         progress: Dict[str, Any] = {}
+        incr = None
         try:
+            if content_digests:
+                from .engine.incremental import IncrementalTake, resolve_base
+
+                if base_root is not None:
+                    resolve_base(base_root, path)  # against rank 0's path, which won
+                incr = IncrementalTake(path, base_root)
             with roctx_range("hipsnapshot.take.plan_and_stage"):
                 pending, metadata = cls._take_impl(path, app_state, rep, keys, comm, storage,
                                                    loop, False, _custom_tensor_prepare_func,
-                                                   quantize, compression, progress=progress)
+                                                   quantize, compression, progress=progress,
+                                                   incr=incr)
             t_staged = time.monotonic()
             with roctx_range("hipsnapshot.take.drain_io"), timeline.span("drain_io"):
                 pending.sync_complete(loop)
+            if incr is not None:
+                # blobs this take points at without writing them keep the
+                # checksum their own take recorded: verify() reads them too
+                pending.stats.checksums.update(incr.reused_sums)
+                storage.sync_write(WriteIO(path=incr.content_path(comm.get_rank()),
+                                           buf=incr.content_doc()), loop)
             _write_checksums(storage, loop, comm.get_rank(), comm.get_world_size(),
                              pending.stats.checksums)
             with roctx_range("hipsnapshot.take.commit"), timeline.span("commit"):
                 with timeline.span("commit_barrier", "commit"):
                     comm.barrier()
                 if comm.get_rank() == 0:
+                    bases = incr.bases_doc(metadata.manifest) if incr is not None else None
+                    if bases is not None:
+                        storage.sync_write(WriteIO(path=incr.BASES_FNAME, buf=bases), loop)
                     with timeline.span("write_metadata", "commit"):
                         cls._write_snapshot_metadata(metadata, storage, loop)
+                    if incr is not None:
+                        incr.drop_content_beyond(comm.get_world_size())
                 if not comm.solo():
                     # take() returns on every rank only once the snapshot is
                     # committed: a rank may read it right away (the reference
@@ -435,6 +476,10 @@ class Snapshot:
         timeline.dump("take", comm.get_rank())
         TakeStats.last = {"stage_s": t_staged - t0, "total_s": time.monotonic() - t0,
                           "bytes": float(pending.stats.bytes_written)}
+        if incr is not None:
+            TakeStats.last.update(bytes_reused=float(incr.bytes_reused),
+                                  leaves_reused=float(incr.leaves_reused),
+                                  digest_s=incr.digest_s)
         snap = cls(path=path, pg=pg, storage_options=storage_options)
         snap._metadata = metadata
         return snap
@@ -520,7 +565,8 @@ class Snapshot:
     @classmethod
     def _open_and_coalesce(cls, path: str, comm: Comm, app_state: AppState,
                            replicated: Optional[List[str]], loop: asyncio.AbstractEventLoop,
-                           storage_options: Optional[Dict[str, Any]]):
+                           storage_options: Optional[Dict[str, Any]],
+                           incremental: Optional[Tuple[Optional[str]]] = None):
         """Commit rule (reference `snapshot.py:226-234`): a snapshot exists
         iff its ``.snapshot_metadata`` exists.  A take into a path that holds
         a committed snapshot overwrites its blobs, so rank 0 takes the old
@@ -540,7 +586,8 @@ class Snapshot:
                 with timeline.span("uncommit"):
                     stash = cls._uncommit(storage, loop)
             with timeline.span("coalesce"):
-                path, rep, keys, nonce = cls._coalesce(path, comm, app_state, replicated or [])
+                path, rep, keys, nonce = cls._coalesce(path, comm, app_state, replicated or [],
+                                                       incremental)
             if storage is None:
                 with timeline.span("storage_open"):
                     storage = url_to_storage_plugin_in_event_loop(path, loop, storage_options)
@@ -556,7 +603,30 @@ class Snapshot:
                 storage.sync_delete(stash[1], loop)
             except Exception as e:  # noqa: BLE001
                 logger.debug(f"could not remove the stashed metadata: {e}")
+        if comm.get_rank() == 0:
+            # only now that the take goes ahead (a failed coalesce puts the
+            # old commit back whole, side files included)
+            cls._drop_stale_side_files(storage, keep_content=incremental is not None)
         return path, rep, keys, nonce, storage
+
+    @staticmethod
+    def _drop_stale_side_files(storage: StoragePlugin, keep_content: bool) -> None:
+        """An earlier incremental take's side files describe blobs this take
+        replaces: a take with content digests rewrites them, any other
+        removes them (local file systems only: nothing else can hold them)."""
+        root = getattr(storage, "root", None)
+        if not (isinstance(storage, _FSStoragePlugin) and isinstance(root, str)):
+            return
+        from .engine import incremental
+
+        try:
+            os.remove(os.path.join(root, incremental.BASES_FNAME))
+        except OSError:
+            pass
+        if not keep_content and os.path.isdir(os.path.join(root, incremental.CONTENT_DIR)):
+            import shutil
+
+            shutil.rmtree(os.path.join(root, incremental.CONTENT_DIR), ignore_errors=True)
 
     @staticmethod
     def _uncommit(storage: StoragePlugin, loop: asyncio.AbstractEventLoop):
@@ -623,7 +693,7 @@ class Snapshot:
                    prepare_func: Optional[PrepareFunc], quantize: Optional[List[str]],
                    compression: Optional[str] = None,
                    progress: Optional[Dict[str, Any]] = None,
-                   ) -> Tuple[PendingIOWork, SnapshotMetadata]:
+                   incr=None) -> Tuple[PendingIOWork, SnapshotMetadata]:
         app_state = dict(app_state)
         rng_item = cls._pop_rng_state(app_state)
         manifest: Dict[str, Entry] = {}
@@ -668,7 +738,9 @@ class Snapshot:
         # from an earlier take still holds are not planned again
         plan = cache_key = None
         resident: Dict[str, Any] = {}
-        if not rep_paths and prepare_func is None and plan_cache.enabled():
+        # (never for a take with content digests or a base: cached entries and
+        # their JSON must not carry locations rewritten into a base)
+        if not rep_paths and prepare_func is None and incr is None and plan_cache.enabled():
             with timeline.span("plan_lookup"):
                 resident = {k: v for k, v in flattened.items() if plan_cache.is_resident(v)}
                 if resident:
@@ -726,6 +798,12 @@ class Snapshot:
             with timeline.span("partition"):
                 object_entries, path_reqs = partition_write_reqs(object_entries, path_reqs,
                                                                  comm)
+        if incr is not None:
+            # content digests of the leaves this rank would write; with a
+            # base, the unchanged ones leave here: batching, compression
+            # planning and rebalancing see only what remains
+            with timeline.span("content_digests"):
+                incr.plan(object_entries, path_reqs, rank, quantize)
         write_reqs = [wr for wrs in path_reqs.values() for wr in wrs]
         if not knobs.is_batching_disabled():
             with timeline.span("batch"):
@@ -1006,6 +1084,29 @@ class Snapshot:
         return verify_snapshot(self.path, self._storage_options, concurrency,
                                distributed=distributed, pg=self.pg)
 
+    def dependencies(self) -> List[str]:
+        """The snapshot directories (absolute paths) this snapshot's entries
+        point into: the bases of an incremental take (``take(base=...)``),
+        which must outlive it.  Empty for a self-contained snapshot."""
+        from .engine import incremental
+
+        root = incremental.fs_root(self.path)
+        return [] if root is None else incremental.read_dependencies(root)
+
+    def materialize(self) -> "Snapshot":
+        """Make this snapshot self-contained: every blob it references in a
+        base is hard-linked (copied where linking fails) into its own
+        directory and its metadata, checksum and content files are re-pointed;
+        afterwards ``dependencies()`` is empty and the bases may be deleted."""
+        from .engine import incremental
+
+        root = incremental.fs_root(self.path)
+        if root is None:
+            raise ValueError("materialize() needs a snapshot on the local 'fs' storage plugin")
+        incremental.materialize(root, self._storage_options)
+        self._metadata = None
+        return self
+
     def read_object(self, path: str, obj_out: Optional[T] = None,
                     memory_budget_bytes: Optional[int] = None, verify: bool = False) -> T:
         """Read one persisted object by manifest path ``RANK/STATEFUL/KEY/...``.
@@ -1108,18 +1209,24 @@ class Snapshot:
         return out
 
     @classmethod
-    def _coalesce(cls, path: str, comm: Comm, app_state: AppState, replicated: List[str]
+    def _coalesce(cls, path: str, comm: Comm, app_state: AppState, replicated: List[str],
+                  incremental: Optional[Tuple[Optional[str]]] = None
                   ) -> Tuple[str, Set[str], List[str], str]:
         """ONE all-gather: path (rank 0 wins), replication globs (intersection),
-        app-state keys (sorted union), hostnames (local world size), nonce."""
+        app-state keys (sorted union), hostnames (local world size), nonce,
+        and what an incremental take must agree on (the resolved base)."""
         rank, ws = comm.get_rank(), comm.get_world_size()
         mode = knobs.get_state_dict_barriers()
         local = mode == "never" or (mode == "auto" and all(
             _state_dict_is_local(v) for v in app_state.values()))
         mine = (path, cls._infer_replicated(replicated, app_state), list(app_state.keys()),
-                socket.gethostname(), uuid.uuid4().hex, local)
+                socket.gethostname(), uuid.uuid4().hex, local, incremental)
         gathered: List[Any] = [None] * ws
         comm.all_gather_object(gathered, mine, frame=4096)
+        if len({g[6] for g in gathered}) > 1:
+            # every rank sees the same gathered values and raises
+            raise ValueError("every rank of an incremental take must pass the same base= and "
+                             f"content_digests=: {[g[6] for g in gathered]}")
         # per-key barriers only when some rank's state_dict() may run a
         # collective (every rank sees the same gathered flags)
         comm.state_dict_barriers = not comm.solo() and not all(g[5] for g in gathered)
