@@ -18,6 +18,11 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 HSIO_SO = os.path.join(PKG_DIR, "_hsio.so")
 HSGPU_SO = os.path.join(PKG_DIR, "_hsgpu.so")
+# The exported C ABI is declared once, in these headers (hsgpu_hooks.h
+# includes hsgpu_abi.h); an exported definition without a prototype is an
+# error, so a signature cannot change without its header.
+HSIO_HDRS = [os.path.join(CSRC, "hsio_abi.h")]
+HSGPU_HDRS = [os.path.join(CSRC, "hsgpu_abi.h"), os.path.join(CSRC, "hsgpu_hooks.h")]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # The kernels use gfx950-only builtins (MFMA 32x32x16 bf16, fp8 conversions):
 # build for gfx950 whatever else PYTORCH_ROCM_ARCH lists (ROCm images often
@@ -58,13 +63,21 @@ def _atomic_build(out: str, cmd_for) -> None:
     os.replace(tmp, out)
 
 
+def _missing_prototype_flag(cxx: str) -> str:
+    # g++ spells it -Wmissing-declarations; clang has that name for something
+    # else and checks functions under -Wmissing-prototypes
+    clang = "clang" in os.path.basename(os.path.realpath(cxx))
+    return "-Werror=missing-prototypes" if clang else "-Werror=missing-declarations"
+
+
 def build_hsio(force: bool = False) -> str:
     srcs = [os.path.join(CSRC, "hsio.cpp"), os.path.join(CSRC, "hsz_cpu.cpp"),
             os.path.join(CSRC, "hschk.cpp")]
-    if force or _stale(HSIO_SO, srcs):
+    if force or _stale(HSIO_SO, srcs + HSIO_HDRS):
         cxx = shutil.which("g++") or shutil.which("c++") or os.path.join(ROCM, "llvm/bin/clang++")
         _atomic_build(HSIO_SO, lambda out: [cxx, "-O3", "-std=c++17", "-fPIC", "-shared",
-                                            "-pthread", "-Wall", "-o", out] + srcs)
+                                            "-pthread", "-Wall", _missing_prototype_flag(cxx),
+                                            "-o", out] + srcs)
     return HSIO_SO
 
 
@@ -74,13 +87,15 @@ def build_hsgpu(force: bool = False, arch: str = "") -> str:
     srcs = [os.path.join(CSRC, "hsgpu.hip"), os.path.join(CSRC, "hsz.hip"),
             os.path.join(CSRC, "hsdma.hip"), os.path.join(CSRC, "hshost.hip"),
             os.path.join(CSRC, "hsdrain.cpp"), os.path.join(CSRC, "hsrestore.cpp")]
-    if force or _stale(HSGPU_SO, srcs):
+    if force or _stale(HSGPU_SO, srcs + HSGPU_HDRS):
         hipcc = os.path.join(ROCM, "bin", "hipcc")
         if not os.path.exists(hipcc):
             hipcc = shutil.which("hipcc") or hipcc
         archs = [f"--offload-arch={a}" for a in gpu_archs(arch)]
         _atomic_build(HSGPU_SO, lambda out: [hipcc] + archs + ["-O3", "-std=c++17", "-fPIC",
-                                                               "-shared", "-Wall", "-o", out]
+                                                               "-shared", "-Wall",
+                                                               "-Werror=missing-prototypes",
+                                                               "-o", out]
                       + srcs + ["-ldl"])
     return HSGPU_SO
 

@@ -20,6 +20,8 @@
 #include <thread>
 #include <vector>
 
+#include "hsio_abi.h"
+
 namespace {
 
 constexpr uint64_t kM1 = 0x9E3779B97F4A7C15ull;

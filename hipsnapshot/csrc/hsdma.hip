@@ -34,6 +34,8 @@
 #include <mutex>
 #include <vector>
 
+#include "hsgpu_hooks.h"
+
 namespace {
 
 struct HsaApi {
@@ -387,9 +389,6 @@ int hsg_sdma_h2d(int dev, void* dst, const void* src, uint64_t n) {
 // *handle naming its completion signal (pass it to hsg_sdma_wait exactly
 // once; `src` and `dst` stay valid until then).  The native restore keeps
 // several uploads queued so the link never idles between them.
-int hsg_sdma_h2d_submit_on(int dev, void* dst, const void* src, uint64_t n, int engine,
-                           uint64_t* handle);
-
 int hsg_sdma_h2d_submit(int dev, void* dst, const void* src, uint64_t n, uint64_t* handle) {
   return hsg_sdma_h2d_submit_on(dev, dst, src, n, -1, handle);
 }

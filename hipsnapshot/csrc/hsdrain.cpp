@@ -51,36 +51,15 @@
 #include <thread>
 #include <vector>
 
-extern "C" {
-int hsg_sdma_d2h_submit(int dev, void* dst, const void* src, uint64_t n, void* stream,
-                        uint64_t* handle);
-int hsg_sdma_wait(uint64_t handle);
-int hsg_sdma_release(int dev, void* stream);
-int hsg_sdma_d2h_submit_released(int dev, void* dst, const void* src, uint64_t n,
-                                 uint64_t* handle);
-void* hsg_copy_stream(int dev, int slot);
-int hsg_stream_priority(int dev, int slot, int high);
-int hsg_hash64(int dev, int slot, int after_slot, const void* p, uint64_t n,
-               uint64_t first_word, int max_grid, int* handle);
-int hsg_hash64_result(int dev, int slot, int handle, uint64_t* out);
-void* hsg_pinned_acquire(uint64_t nbytes);
-int hsg_pinned_release(void* p);
-int hsg_rt_set_device(int dev);
-}
+#include "hsgpu_hooks.h"
 
 namespace {
 
 constexpr int kDrainCopySlot = 1000;  // idle stream the SDMA submits order after
 constexpr int kDrainHashSlot = 1001;     // high priority
-constexpr int kDrainHashSlotLow = 1002;  // default priority (kFlagHashLowPrio)
+constexpr int kDrainHashSlotLow = 1002;  // default priority (HSG_DRAIN_HASH_LOW_PRIO)
 constexpr int kHashLag = 256;         // results collected this many blobs behind
-constexpr int kFlagSync = 1;
-constexpr int kFlagHash = 2;
-constexpr int kFlagDirect = 4;  // O_DIRECT: the engines' slots go to the device, no CPU copy
-constexpr int kFlagHashLowPrio = 8;  // keep the hash stream at default priority
 constexpr uint64_t kDirectAlign = 4096;
-constexpr int kNiceShift = 8;  // flags bits 8..15: nice increment of the drain threads
-constexpr int kParkedShift = 16;  // flags bits 16..23: parked writers (hsg_drain_boost)
 
 // Lower this thread's CPU priority by `inc` (Linux: per-thread nice).  The
 // drain's threads then yield a shared core to the trainer's launch thread
@@ -134,9 +113,9 @@ enum Stat {
   kPwrite,       // writers in pwrite
   kClose,        // writers trimming / syncing / closing files
   kOpen,         // dma thread creating directories and opening files
-  kWall,
-  kNumStats
+  kWall
 };
+static_assert(kWall + 1 == HSG_DRAIN_NUM_STATS, "Stat and the ABI's stat count differ");
 
 uint64_t now_ns() {
   return static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -144,7 +123,7 @@ uint64_t now_ns() {
 }
 
 struct Job {
-  std::atomic<uint64_t> ns[kNumStats] = {};
+  std::atomic<uint64_t> ns[HSG_DRAIN_NUM_STATS] = {};
   uint64_t t_start = 0;
   void add(Stat k, uint64_t t0) { ns[k].fetch_add(now_ns() - t0); }
   int dev;
@@ -162,7 +141,7 @@ struct Job {
   bool submit_done = false;
   bool wait_done = false;
   std::atomic<int> err{0};
-  char errmsg[256] = {0};
+  char errmsg[HSG_DRAIN_MSG_BYTES] = {0};
   std::atomic<uint64_t> bytes_written{0};
   std::atomic<int> blobs_left{0};
 
@@ -188,17 +167,17 @@ void close_blob(Job* j, Blob& b) {
   if (fstat(b.fd, &st) == 0 && uint64_t(st.st_size) != b.nbytes) {
     if (ftruncate(b.fd, off_t(b.nbytes)) != 0) j->fail(-errno, "ftruncate", b.path);
   }
-  if ((j->flags & kFlagSync) && fdatasync(b.fd) != 0) j->fail(-errno, "fdatasync", b.path);
+  if ((j->flags & HSG_DRAIN_SYNC) && fdatasync(b.fd) != 0) j->fail(-errno, "fdatasync", b.path);
   close(b.fd);
   b.fd = -1;
   j->add(kClose, t0);
 }
 
 void dma_thread(Job* j) {
-  lower_priority((j->flags >> kNiceShift) & 0xff);
+  lower_priority((j->flags >> HSG_DRAIN_NICE_SHIFT) & 0xff);
   // hashes run at high stream priority: a narrow grid that must not wait
   // for a training step's workgroups to drain (hsg_stream_priority)
-  const int hash_slot = (j->flags & kFlagHashLowPrio) ? kDrainHashSlotLow : kDrainHashSlot;
+  const int hash_slot = (j->flags & HSG_DRAIN_HASH_LOW_PRIO) ? kDrainHashSlotLow : kDrainHashSlot;
   if (hash_slot == kDrainHashSlot) hsg_stream_priority(j->dev, kDrainHashSlot, 1);
   void* stream = hsg_copy_stream(j->dev, kDrainCopySlot);
   // the arena is frozen (the caller waited for the freeze): ONE system-scope
@@ -224,7 +203,7 @@ void dma_thread(Job* j) {
     Blob& b = j->blobs[i];
     uint64_t t0 = now_ns();
     int r = mkdirs(b.path);
-    if (r == 0 && (j->flags & kFlagDirect)) {
+    if (r == 0 && (j->flags & HSG_DRAIN_DIRECT)) {
       b.fd = open(b.path.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC | O_DIRECT, 0644);
       b.direct = b.fd >= 0;  // EINVAL: the filesystem has no O_DIRECT (tmpfs)
     }
@@ -238,7 +217,7 @@ void dma_thread(Job* j) {
       break;
     }
     t0 = now_ns();
-    if (j->flags & kFlagHash) {
+    if (j->flags & HSG_DRAIN_HASH) {
       if (hsg_hash64(j->dev, hash_slot, -1, reinterpret_cast<const void*>(b.src),
                      b.nbytes, 0, j->max_hash_grid, &b.hash_handle) != 0) {
         j->fail(-EIO, "hash launch", b.path);
@@ -293,7 +272,7 @@ void dma_thread(Job* j) {
 }
 
 void wait_thread(Job* j) {
-  lower_priority((j->flags >> kNiceShift) & 0xff);
+  lower_priority((j->flags >> HSG_DRAIN_NICE_SHIFT) & 0xff);
   for (;;) {
     Chunk c;
     {
@@ -339,7 +318,7 @@ void widen_affinity() {
 // the drain ran at 44.7 GB/s with 16 niced writers off the caller's core, at
 // 49.5 GB/s without those restrictions (profiles/r5/zero3_ab/).
 void writer_thread(Job* j, bool parked) {
-  if (!parked) lower_priority((j->flags >> kNiceShift) & 0xff);
+  if (!parked) lower_priority((j->flags >> HSG_DRAIN_NICE_SHIFT) & 0xff);
   bool widened = false;
   for (;;) {
     Chunk c;
@@ -400,13 +379,8 @@ extern "C" {
 // Start draining `n` blobs: blob i is device bytes [srcs[i], srcs[i] +
 // sizes[i]) -> file paths[i] (created with parent directories, overwritten
 // in place, trimmed to size).  `nslots` pinned slots of `slot_bytes` move
-// the data; `nwriters` threads write it.  flags: 1 = fdatasync every file,
-// 2 = hs64 hash every blob on the GPU (narrow grid `max_hash_grid`), 4 =
-// O_DIRECT files (the pinned slots go to the device with no CPU copy and no
-// page cache; buffered where the filesystem refuses it), 8 = hash stream at
-// default instead of high priority, bits 8..15 = nice
-// increment of every drain thread, bits 16..23 = parked writers that start
-// on hsg_drain_boost.
+// the data; `nwriters` threads write it.  `flags`: the HSG_DRAIN_* bits and
+// fields of hsgpu_abi.h (hashes run on a narrow grid of `max_hash_grid`).
 // Returns a handle (> 0) for hsg_drain_wait, or 0 with *err set.
 void* hsg_drain_start(int dev, int n, const uint64_t* srcs, const uint64_t* sizes,
                       const char* const* paths, uint64_t slot_bytes, int nslots, int nwriters,
@@ -440,13 +414,13 @@ void* hsg_drain_start(int dev, int n, const uint64_t* srcs, const uint64_t* size
     }
     j->slots.push_back(p);
     j->free_slots.push_back(s);
-    if (reinterpret_cast<uintptr_t>(p) % kDirectAlign) j->flags &= ~kFlagDirect;
+    if (reinterpret_cast<uintptr_t>(p) % kDirectAlign) j->flags &= ~HSG_DRAIN_DIRECT;
   }
   j->t_start = now_ns();
   j->threads.emplace_back(dma_thread, j);
   j->threads.emplace_back(wait_thread, j);
   for (int w = 0; w < std::max(nwriters, 1); ++w) j->threads.emplace_back(writer_thread, j, false);
-  for (int w = 0; w < ((flags >> kParkedShift) & 0xff); ++w)
+  for (int w = 0; w < ((flags >> HSG_DRAIN_PARKED_SHIFT) & 0xff); ++w)
     j->threads.emplace_back(writer_thread, j, true);
   return j;
 }
@@ -463,16 +437,16 @@ void hsg_drain_boost(void* handle) {
 
 // Wait for the drain (blocking; Python calls it without the GIL).  Returns 0
 // or the first error (negative errno); `sums` (n entries, may be null)
-// receives each blob's hs64 partial sum; `msg` (>= 256 bytes, may be null)
-// the error text; `stats` (kNumStats doubles, may be null) the seconds per
-// Stat.  Frees the job: call exactly once per handle.
+// receives each blob's hs64 partial sum; `msg` (>= HSG_DRAIN_MSG_BYTES, may
+// be null) the error text; `stats` (HSG_DRAIN_NUM_STATS doubles, may be null)
+// the seconds per Stat.  Frees the job: call exactly once per handle.
 int hsg_drain_wait(void* handle, uint64_t* sums, uint64_t* bytes_written, char* msg,
                    double* stats) {
   Job* j = static_cast<Job*>(handle);
   for (auto& t : j->threads) t.join();
   j->add(kWall, j->t_start);
   if (stats)
-    for (int k = 0; k < kNumStats; ++k) stats[k] = 1e-9 * double(j->ns[k].load());
+    for (int k = 0; k < HSG_DRAIN_NUM_STATS; ++k) stats[k] = 1e-9 * double(j->ns[k].load());
   for (auto& b : j->blobs)
     if (b.fd >= 0) close(b.fd);
   for (void* p : j->slots) hsg_pinned_release(p);
@@ -480,7 +454,7 @@ int hsg_drain_wait(void* handle, uint64_t* sums, uint64_t* bytes_written, char* 
   if (sums)
     for (size_t i = 0; i < j->blobs.size(); ++i) sums[i] = j->blobs[i].sum;
   if (bytes_written) *bytes_written = j->bytes_written.load();
-  if (msg) snprintf(msg, 256, "%s", j->errmsg);
+  if (msg) snprintf(msg, HSG_DRAIN_MSG_BYTES, "%s", j->errmsg);
   delete j;
   return e;
 }

@@ -46,6 +46,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "hsgpu_hooks.h"
+
 namespace {
 
 constexpr int kMaxDims = 8;
@@ -1675,7 +1677,7 @@ struct MappedBlock {
 std::mutex g_mapped_mu;
 std::unordered_map<void*, MappedBlock> g_mapped;  // registered block -> its mapping
 
-void* alloc_thp_registered(size_t want, int node = -1) {
+static void* alloc_thp_registered(size_t want, int node = -1) {
   constexpr size_t kHuge = size_t(2) << 20;
   const size_t len = want + kHuge;
   void* base = mmap(nullptr, len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
@@ -1727,7 +1729,7 @@ void* alloc_thp_registered(size_t want, int node = -1) {
   return p;
 }
 
-void free_pinned_block(void* p) {
+static void free_pinned_block(void* p) {
   {
     std::lock_guard<std::mutex> g(g_pool.mu);
     g_pool.node.erase(p);
@@ -1866,8 +1868,6 @@ uint64_t hsg_pinned_trim() {
   return freed;
 }
 
-int hsg_restore_idle_blocks(int dev, uint64_t* ptrs, uint64_t* sizes, int max);
-
 // Test hook: overwrite every idle block of the restore's device pools (on
 // `dev`) and of the pinned host pool with `byte`, so a test can show that no
 // restore reads bytes an earlier one left behind.  Returns the blocks written.
@@ -1899,10 +1899,6 @@ int hsg_poison_idle_pools(int dev, int byte) {
 // hipDeviceMallocUncached memory, cached per device by size (best fit up to
 // 2x, 2 MiB granules): the restore's encoded frames are uploaded into it by
 // SDMA and read once by the decode kernel, never through a stale L2 line.
-extern "C" void* hsg_rt_vmm_alloc(int dev, uint64_t nbytes, int uncached);
-extern "C" int hsg_rt_vmm_free(void* p);
-extern "C" const char* hsg_rt_last_error();
-
 struct UncachedPool {
   std::mutex mu;
   std::map<int, std::multimap<size_t, void*>> free_blocks;  // dev -> size -> block
@@ -2058,7 +2054,7 @@ struct HashRing {
 std::mutex g_hash_mu;
 std::map<int, HashRing> g_hash_rings;
 
-int hash_ring(int dev, HashRing** out) {
+static int hash_ring(int dev, HashRing** out) {
   std::lock_guard<std::mutex> g(g_hash_mu);
   HashRing& h = g_hash_rings[dev];
   if (h.acc == nullptr) {

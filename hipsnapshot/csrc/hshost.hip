@@ -17,6 +17,8 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "hsgpu_hooks.h"
+
 namespace {
 
 // The last failed runtime call of these hooks, with HIP's error name: the

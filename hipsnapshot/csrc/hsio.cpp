@@ -44,19 +44,10 @@
 #include <utility>
 #include <vector>
 
+#include "hsio_abi.h"
+
 namespace {
 
-constexpr int kFlagDirect = 1;   // try O_DIRECT for the aligned body
-constexpr int kFlagSync = 2;     // fdatasync before completing a write
-constexpr int kFlagMkdirs = 4;   // create parent directories
-constexpr int kFlagAppend = 8;   // write at offset without truncating
-// bits 16..23: NUMA node + 1 whose CPUs run the job (0: any).  A blob
-// written straight from host pages (a host-resident UVM table) is copied into
-// the page cache by the worker's CPU: a worker on the pages' node reads them
-// locally.  Unbound, the workers landed on either socket and an 8 GB DLRM
-// UVM save spread 36-69 GB/s; bound to the wrong node it ran 30-43
-// (profiles/r6/dlrm_var/).
-constexpr int kNodeShift = 16;
 constexpr size_t kAlign = 4096;
 constexpr size_t kMaxIo = size_t(1) << 30;  // keep single syscalls < 2 GiB
 
@@ -209,7 +200,7 @@ class Engine {
         j = std::move(queue_.front());
         queue_.pop_front();
       }
-      PlaceFor(((j.flags >> kNodeShift) & 0xff) - 1);
+      PlaceFor(((j.flags >> HSIO_NODE_SHIFT) & 0xff) - 1);
       int64_t r = Execute(j);
       int64_t id = j.id;
       if (j.group) {
@@ -317,7 +308,7 @@ class Engine {
   }
 
   int64_t DoWrite(const Job& j) {
-    if (j.flags & kFlagMkdirs) {
+    if (j.flags & HSIO_MKDIRS) {
       int r = MkdirsFor(j.path);
       if (r < 0) return r;
     }
@@ -327,7 +318,7 @@ class Engine {
     // the stale tail, if any, is cut with ftruncate below.
     int oflags = O_WRONLY | O_CREAT | O_CLOEXEC;
     int fd = ::open(j.path.c_str(), oflags, 0644);
-    if (fd < 0 && errno == ENOENT && (j.flags & kFlagMkdirs)) {
+    if (fd < 0 && errno == ENOENT && (j.flags & HSIO_MKDIRS)) {
       // the cached parent was removed since (e.g. a directory of a previous
       // take deleted by its successor): forget it, recreate, retry once
       ForgetDirOf(j.path);
@@ -339,7 +330,7 @@ class Engine {
     int64_t res = 0;
     size_t body = 0;
     bool aligned = (reinterpret_cast<uintptr_t>(j.buf) % kAlign == 0) && (j.offset % kAlign == 0);
-    if ((j.flags & kFlagDirect) && aligned && j.nbytes >= kAlign) {
+    if ((j.flags & HSIO_DIRECT) && aligned && j.nbytes >= kAlign) {
       body = j.nbytes / kAlign * kAlign;
       int dfd = ::open(j.path.c_str(), O_WRONLY | O_CLOEXEC | O_DIRECT);
       if (dfd >= 0) {
@@ -351,13 +342,13 @@ class Engine {
       }
     }
     res = full_pwrite(fd, j.buf + body, j.nbytes - body, j.offset + body);
-    if (res >= 0 && !(j.flags & kFlagAppend) && j.offset == 0) {
+    if (res >= 0 && !(j.flags & HSIO_APPEND) && j.offset == 0) {
       struct stat st;
       if (::fstat(fd, &st) == 0 && static_cast<size_t>(st.st_size) != j.nbytes) {
         if (::ftruncate(fd, static_cast<off_t>(j.nbytes)) != 0) res = -errno;
       }
     }
-    if (res >= 0 && (j.flags & kFlagSync)) {
+    if (res >= 0 && (j.flags & HSIO_SYNC)) {
       if (::fdatasync(fd) != 0) res = -errno;
     }
     ::close(fd);
@@ -370,7 +361,7 @@ class Engine {
     size_t body = 0;
     int64_t got = 0;
     bool aligned = (reinterpret_cast<uintptr_t>(j.buf) % kAlign == 0) && (j.offset % kAlign == 0);
-    if ((j.flags & kFlagDirect) && aligned && j.nbytes >= kAlign) {
+    if ((j.flags & HSIO_DIRECT) && aligned && j.nbytes >= kAlign) {
       body = j.nbytes / kAlign * kAlign;
       int dfd = ::open(j.path.c_str(), O_RDONLY | O_CLOEXEC | O_DIRECT);
       if (dfd >= 0) {

@@ -59,44 +59,13 @@
 #include <unordered_map>
 #include <vector>
 
-extern "C" {
-int hsg_sdma_h2d_submit_on(int dev, void* dst, const void* src, uint64_t n, int engine,
-                           uint64_t* handle);
-uint32_t hsg_sdma_h2d_engine_mask(int dev);
-int hsg_sdma_wait(uint64_t handle);
-void* hsg_pinned_acquire(uint64_t nbytes);
-int hsg_pinned_release(void* p);
-int hsg_hsz_decode(int dev, const void* frames, const void* offsets, uint32_t first,
-                   uint32_t count, uint64_t logical, int w, uint32_t frame_bytes, void* out,
-                   void* stream, void* err);
-uint64_t hsg_copy_workspace_bytes(const void* descs, int n);
-int hsg_copy_nd(int dev, const void* descs, int n, void* workspace, uint64_t ws_bytes,
-                void* pinned_stage, void* stream, int sync);
-uint64_t hsg_desc_size();
-void* hsg_copy_stream(int dev, int slot);
-int hsg_rt_set_device(int dev);
-void* hsg_rt_vmm_alloc(int dev, uint64_t nbytes, int uncached);
-int hsg_rt_vmm_free(void* p);
-uint64_t hsg_rt_vmm_retired_bytes();
-void* hsg_rt_event_record(void* stream);
-int hsg_rt_event_sync(void* ev);
-void hsg_rt_event_free(void* ev);
-int hsg_rt_stream_after(void* waiter, void* producer);
-int hsg_rt_stream_sync(void* stream);
-int hsg_rt_memcpy_d2h(void* dst, const void* src, uint64_t n);
-int hsg_hash64_into(int dev, void* stream, const void* p, uint64_t n, uint64_t first_word,
-                    int max_grid, void* acc);
-const char* hsg_rt_last_error();
-void hsg_rt_trace(const char* what, const void* p, uint64_t n, int kind);
-}
+#include "hsgpu_hooks.h"
 
 namespace {
 
 constexpr uint64_t kGranule = uint64_t(2) << 20;
 constexpr uint64_t kHszHeader = 64;
 constexpr uint64_t kHszFrameHeader = 32;
-constexpr int kCodecRaw = 0;
-constexpr int kCodecHsz = 1;
 constexpr int kRestoreSlot = 2000;  // persistent streams (dev, 2000 + s), s = 0, 1
 
 uint64_t now_ns() {
@@ -280,7 +249,7 @@ struct Item {
   std::string path;
   uint64_t file_lo = 0;    // first file byte to read
   uint64_t nbytes = 0;     // bytes to read (the whole stored blob for HSZ1)
-  int codec = kCodecRaw;
+  int codec = HSG_CODEC_RAW;
   uint64_t logical = 0;    // HSZ1: expected logical size
   uint64_t direct = 0;     // HSZ1: decode straight into this device address
   uint64_t base_off = 0;   // region sources start here in the decoded / raw bytes
@@ -341,9 +310,9 @@ enum Stat {
   kRetireWait,   // retire thread waiting for device work
   kFirstUpload,  // start -> first upload submitted
   kUploadBusy,   // time with at least one upload in flight
-  kWall,
-  kNumStats
+  kWall
 };
+static_assert(kWall + 1 == HSG_RESTORE_NUM_STATS, "Stat and the ABI's stat count differ");
 
 struct Job {
   int dev = 0;
@@ -397,8 +366,8 @@ struct Job {
 
   std::atomic<int> err{0};
   int err_item = -1;
-  char errmsg[320] = {0};
-  std::atomic<uint64_t> ns[kNumStats] = {};
+  char errmsg[HSG_RESTORE_MSG_BYTES] = {0};
+  std::atomic<uint64_t> ns[HSG_RESTORE_NUM_STATS] = {};
   std::atomic<uint64_t> bytes_read{0};
   std::atomic<bool> first_upload{false};
   uint64_t t_start = 0;
@@ -430,7 +399,7 @@ int alloc_item_locked(Job* j, int i) {
   Item& it = j->items[i];
   if (it.allocated) return 0;
   const uint64_t nu = align4k(it.nbytes);
-  const uint64_t ns = (it.codec == kCodecHsz && !it.direct) ? align4k(it.logical) : 0;
+  const uint64_t ns = (it.codec == HSG_CODEC_HSZ && !it.direct) ? align4k(it.logical) : 0;
   const bool ring_ok = j->up_ring.base && nu <= j->up_ring.cap &&
                        (ns == 0 || (j->sc_ring.base && ns <= j->sc_ring.cap));
   if (ring_ok) {
@@ -573,7 +542,7 @@ void reader_thread(Job* j) {
     if (f.left.fetch_sub(1) != 1) continue;
     // the slot is full: upload it
     const char* sp = static_cast<const char*>(j->slots[s]);
-    if (f.chunk == 0 && it.codec == kCodecHsz) {
+    if (f.chunk == 0 && it.codec == HSG_CODEC_HSZ) {
       // header + frame table: validated once every chunk has landed
       uint64_t nf = 0;
       memcpy(&nf, sp + 24, 4);
@@ -650,7 +619,7 @@ int launch_item(Job* j, int i, void* s) {
     j->fail(-EIO, i, "hash launch");
     return -1;
   }
-  if (it.codec == kCodecHsz) {
+  if (it.codec == HSG_CODEC_HSZ) {
     int w;
     uint32_t fb, nf;
     if (!hsz_header_ok(it, &w, &fb, &nf)) {
@@ -862,7 +831,7 @@ void* hsg_restore_start(int dev, int n, const char* const* paths, const uint64_t
     }
     it.chunks_left.store(it.nchunks);
     if (desc_off[i] < 0 || desc_off[i] + desc_n[i] > n_descs || it.nchunks == 0 ||
-        (it.codec == kCodecHsz && it.nbytes < kHszHeader)) {
+        (it.codec == HSG_CODEC_HSZ && it.nbytes < kHszHeader)) {
       delete j;
       *err = -3;
       return nullptr;
@@ -894,7 +863,7 @@ void* hsg_restore_start(int dev, int n, const char* const* paths, const uint64_t
   uint64_t need_up = 0, need_sc = 0;
   for (const Item& it : j->items) {
     need_up += align4k(it.nbytes);
-    if (it.codec == kCodecHsz && !it.direct) need_sc += align4k(it.logical);
+    if (it.codec == HSG_CODEC_HSZ && !it.direct) need_sc += align4k(it.logical);
   }
   const uint64_t cap_up = std::min(j->budget, need_up), cap_sc = std::min(j->budget, need_sc);
   if (cap_up) j->up_base = g_upload_pool.acquire(dev, cap_up);
@@ -976,8 +945,9 @@ void* hsg_restore_start(int dev, int n, const char* const* paths, const uint64_t
 
 // Wait for the restore (blocking; Python calls it without the GIL).  Returns
 // 0 or the first error (negative errno); *err_item = the item it concerns
-// (-1: none); `msg` (>= 320 bytes) its text; `stats` (kNumStats doubles:
-// seconds) where the time went; *bytes_read the bytes read from files;
+// (-1: none); `msg` (>= HSG_RESTORE_MSG_BYTES) its text; `stats`
+// (HSG_RESTORE_NUM_STATS doubles: seconds) where the time went; *bytes_read
+// the bytes read from files;
 // `sums` (n entries, nullable) the hs64 partial sums of the hashed items'
 // stored bytes (0 for the others).
 // Everything launched has finished when this returns (decode error words
@@ -1008,12 +978,12 @@ int hsg_restore_wait(void* handle, int* err_item, char* msg, double* stats,
   for (void* p : j->slots)
     if (p) hsg_pinned_release(p);
   if (stats)
-    for (int k = 0; k < kNumStats; ++k) stats[k] = 1e-9 * double(j->ns[k].load());
+    for (int k = 0; k < HSG_RESTORE_NUM_STATS; ++k) stats[k] = 1e-9 * double(j->ns[k].load());
   if (bytes_read) *bytes_read = j->bytes_read.load();
   const int e = j->err.load();
   hsg_rt_trace("job-end", j, uint64_t(-e), j->err_item);
   if (err_item) *err_item = j->err_item;
-  if (msg) snprintf(msg, 320, "%s", j->errmsg);
+  if (msg) snprintf(msg, HSG_RESTORE_MSG_BYTES, "%s", j->errmsg);
   delete j;
   return e;
 }

@@ -46,7 +46,7 @@
 #include <cstdlib>
 #include <cstdio>
 
-extern "C" int hsg_thread_grid_cap();  // hsgpu.hip
+#include "hsgpu_hooks.h"
 
 namespace {
 

@@ -13,6 +13,8 @@
 #include <thread>
 #include <vector>
 
+#include "hsio_abi.h"
+
 namespace {
 
 constexpr int kSample = 2048;

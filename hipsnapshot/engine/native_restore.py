@@ -40,7 +40,7 @@ logger = logging.getLogger(__name__)
 
 last_stats: Dict[str, float] = {}  # the last job's phase seconds (NativeRestore.STATS)
 
-_RAW, _HSZ = 0, 1
+_RAW, _HSZ = native.CODEC_RAW, native.CODEC_HSZ
 
 
 def _root(storage: StoragePlugin) -> Optional[str]:

@@ -37,19 +37,49 @@ _hsgpu_error: Optional[str] = None
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
 c_int64 = ctypes.c_int64
+c_uint32 = ctypes.c_uint32
 c_uint64 = ctypes.c_uint64
+c_double = ctypes.c_double
 c_char_p = ctypes.c_char_p
+P = ctypes.POINTER
 
 
-def _declare(lib: ctypes.CDLL, name: str, restype, argtypes) -> None:
-    fn = getattr(lib, name)
-    fn.restype = restype
-    fn.argtypes = argtypes
+def _declare(lib: ctypes.CDLL, abi: Dict[str, tuple]) -> None:
+    for name, (restype, argtypes) in abi.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
 
 
 # ---------------------------------------------------------------------------
 # _hsio.so
 # ---------------------------------------------------------------------------
+
+# name -> (restype, argtypes) of everything _hsio.so exports; checked against
+# csrc/hsio_abi.h by tests/test_native_abi.py
+HSIO_ABI = {
+    "hsio_create": (c_void_p, [c_int]),
+    "hsio_destroy": (None, [c_void_p]),
+    "hsio_eventfd": (c_int, [c_void_p]),
+    "hsio_set_read_split": (None, [c_void_p, c_uint64]),
+    "hsio_submit_write": (c_int64, [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int]),
+    "hsio_submit_read": (c_int64, [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int]),
+    "hsio_submit_delete": (c_int64, [c_void_p, c_char_p]),
+    "hsio_poll": (c_int, [c_void_p, P(c_int64), P(c_int64), c_int]),
+    "hsio_write_sync": (c_int64, [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int]),
+    "hsio_read_sync": (c_int64, [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int]),
+    "hsio_file_size": (c_int64, [c_char_p]),
+    "hsio_alloc_aligned": (c_void_p, [c_uint64]),
+    "hsio_free_aligned": (None, [c_void_p]),
+    "hsio_parallel_memcpy": (None, [c_void_p, c_void_p, c_uint64, c_int]),
+    "hs64_partial": (c_uint64, [c_void_p, c_uint64, c_uint64, c_int]),
+    "hs64_finish": (c_uint64, [c_uint64, c_uint64]),
+    "hsz_max_encoded_bytes": (c_uint64, [c_uint64, c_uint32]),
+    "hsz_encode_cpu": (c_int64, [c_void_p, c_uint64, c_int, c_uint32, c_void_p, c_int]),
+    "hsz_decode_cpu": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint64, c_int, c_uint32,
+                               c_void_p, c_int]),
+}
+
 
 def hsio() -> ctypes.CDLL:
     global _hsio_lib
@@ -61,37 +91,12 @@ def hsio() -> ctypes.CDLL:
             if not os.path.exists(path):
                 _build.build_hsio()
             lib = ctypes.CDLL(path)
-            _declare(lib, "hsio_create", c_void_p, [c_int])
-            _declare(lib, "hsio_destroy", None, [c_void_p])
-            _declare(lib, "hsio_eventfd", c_int, [c_void_p])
-            _declare(lib, "hsio_set_read_split", None, [c_void_p, c_uint64])
-            _declare(lib, "hsio_submit_write", c_int64,
-                     [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int])
-            _declare(lib, "hsio_submit_read", c_int64,
-                     [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int])
-            _declare(lib, "hsio_submit_delete", c_int64, [c_void_p, c_char_p])
-            _declare(lib, "hsio_poll", c_int,
-                     [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_int])
-            _declare(lib, "hsio_write_sync", c_int64,
-                     [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int])
-            _declare(lib, "hsio_read_sync", c_int64,
-                     [c_void_p, c_char_p, c_void_p, c_uint64, c_uint64, c_int])
-            _declare(lib, "hsio_file_size", c_int64, [c_char_p])
-            _declare(lib, "hsio_alloc_aligned", c_void_p, [c_uint64])
-            _declare(lib, "hsio_free_aligned", None, [c_void_p])
-            _declare(lib, "hsio_parallel_memcpy", None, [c_void_p, c_void_p, c_uint64, c_int])
-            _declare(lib, "hs64_partial", c_uint64, [c_void_p, c_uint64, c_uint64, c_int])
-            _declare(lib, "hs64_finish", c_uint64, [c_uint64, c_uint64])
-            _declare(lib, "hsz_max_encoded_bytes", c_uint64, [c_uint64, ctypes.c_uint32])
-            _declare(lib, "hsz_encode_cpu", c_int64,
-                     [c_void_p, c_uint64, c_int, ctypes.c_uint32, c_void_p, c_int])
-            _declare(lib, "hsz_decode_cpu", c_int,
-                     [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_uint64, c_int,
-                      ctypes.c_uint32, c_void_p, c_int])
+            _declare(lib, HSIO_ABI)
             _hsio_lib = lib
     return _hsio_lib
 
 
+# `flags` of the submit / sync calls (csrc/hsio_abi.h HSIO_*)
 IO_DIRECT = 1
 IO_SYNC = 2
 IO_MKDIRS = 4
@@ -223,6 +228,96 @@ def gpu_available() -> bool:
     return _gpu_seen
 
 
+# name -> (restype, argtypes) of what Python calls in _hsgpu.so; checked
+# against csrc/hsgpu_abi.h by tests/test_native_abi.py
+HSGPU_ABI = {
+    "hsg_last_error": (c_char_p, []),
+    "hsg_device_count": (c_int, []),
+    "hsg_pci_location": (c_int, [c_int, P(c_int), P(c_int), P(c_int)]),
+    "hsg_pinned_acquire": (c_void_p, [c_uint64]),
+    "hsg_pinned_release": (c_int, [c_void_p]),
+    "hsg_pinned_acquire_on": (c_void_p, [c_uint64, c_int]),
+    "hsg_pinned_stats": (None, [P(c_uint64), P(c_uint64)]),
+    "hsg_pinned_trim": (c_uint64, []),
+    "hsg_pinned_set_limit": (None, [c_uint64]),
+    "hsg_memcpy": (c_int, [c_int, c_int, c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_int,
+                           c_int]),
+    "hsg_stream_join": (c_int, [c_int, c_int, c_void_p]),
+    "hsg_stream_sync": (c_int, [c_int, c_int]),
+    "hsg_copy_stream": (c_void_p, [c_int, c_int]),
+    "hsg_sync_stream_handle": (c_int, [c_void_p]),
+    "hsg_desc_size": (c_uint64, []),
+    "hsg_prewarm_module": (c_int, [c_int]),
+    "hsg_copy_workspace_bytes": (c_uint64, [c_void_p, c_int]),
+    "hsg_copy_nd": (c_int, [c_int, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_int]),
+    "hsg_fp8_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int,
+                                 c_void_p]),
+    "hsg_fp8_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,
+                                   c_void_p]),
+    "hsg_fp8_hadamard_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                          c_void_p]),
+    "hsg_fp8_hadamard_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                            c_void_p]),
+    "hsg_mx8_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "hsg_mx8_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
+                                   c_int, c_int, c_int, c_int, P(c_int)]),
+    "hsg_drain_wait": (c_int, [c_void_p, P(c_uint64), P(c_uint64), c_char_p, P(c_double)]),
+    "hsg_drain_pending": (c_int, [c_void_p]),
+    "hsg_drain_boost": (None, [c_void_p]),
+    "hsg_restore_start": (c_void_p, [c_int, c_int, P(c_char_p), P(c_uint64), P(c_uint64), P(c_int),
+                                     P(c_uint64), P(c_uint64), P(c_uint64), P(c_int64), P(c_int),
+                                     c_void_p, c_int64, P(c_uint64), c_int, c_void_p, c_uint64,
+                                     c_uint64, c_uint64, c_int, c_int, c_uint64, c_int, P(c_int),
+                                     c_int, P(c_int)]),
+    "hsg_restore_wait": (c_int, [c_void_p, P(c_int), c_char_p, P(c_double), P(c_uint64),
+                                 P(c_uint64)]),
+    "hsg_restore_trim": (c_uint64, [c_int, c_uint64]),
+    "hsg_restore_trim_pools": (c_uint64, [c_int, c_uint64, c_uint64]),
+    "hsg_restore_pool_bytes": (None, [c_int, P(c_uint64)]),
+    "hsg_uncached_bytes": (c_uint64, []),
+    "hsg_poison_idle_pools": (c_int, [c_int, c_int]),
+    "hsg_restore_prewarm": (c_int, [c_int, c_uint64, c_uint64, c_uint64, c_int, c_uint64]),
+    "hsg_sdma_h2d_submit": (c_int, [c_int, c_void_p, c_void_p, c_uint64, P(c_uint64)]),
+    "hsg_is_managed": (c_int, [c_void_p]),
+    "hsg_managed_location": (c_int, [c_void_p, c_uint64, P(c_int), P(c_int)]),
+    "hsg_managed_place": (c_int, [c_int, c_void_p, c_uint64, c_int, c_void_p]),
+    "hsg_managed_alloc": (c_void_p, [c_int, c_uint64]),
+    "hsg_managed_free": (c_int, [c_void_p]),
+    "hsg_gate_supported": (c_int, [c_int]),
+    "hsg_gate_arm": (c_int, [c_int, c_void_p, P(c_uint32)]),
+    "hsg_gate_release": (c_int, [c_int, c_uint32]),
+    "hsg_gate_value": (c_uint32, [c_int]),
+    "hsg_hsz_last_error": (c_char_p, []),
+    "hsg_set_thread_grid_cap": (c_int, [c_int]),
+    "hsg_hash64": (c_int, [c_int, c_int, c_int, c_void_p, c_uint64, c_uint64, c_int, P(c_int)]),
+    "hsg_hash64_result": (c_int, [c_int, c_int, c_int, P(c_uint64)]),
+    "hsg_hash64_batch": (c_int, [c_int, c_void_p, c_void_p, c_int, P(c_uint64)]),
+    "hsg_sdma_last_error": (c_char_p, []),
+    "hsg_sdma_engines": (c_int, [c_int]),
+    "hsg_sdma_h2d": (c_int, [c_int, c_void_p, c_void_p, c_uint64]),
+    "hsg_uncached_acquire": (c_void_p, [c_int, c_uint64]),
+    "hsg_uncached_release": (c_int, [c_void_p]),
+    "hsg_uncached_trim": (c_uint64, []),
+    "hsg_rt_dev_alloc": (c_void_p, [c_int, c_uint64, c_int]),
+    "hsg_rt_dev_free": (None, [c_void_p]),
+    "hsg_rt_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_uint64]),
+    "hsg_rt_last_error": (c_char_p, []),
+    "hsg_rt_set_trace": (None, [c_int]),
+    "hsg_rt_vmm_alloc": (c_void_p, [c_int, c_uint64, c_int]),
+    "hsg_rt_vmm_free": (c_int, [c_void_p]),
+    "hsg_rt_vmm_retired_bytes": (c_uint64, []),
+    "hsg_sdma_d2h": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_int, c_void_p]),
+    "hsg_sdma_d2h_submit": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_void_p, P(c_uint64)]),
+    "hsg_sdma_wait": (c_int, [c_uint64]),
+    "hsg_hsz_meta_bytes": (c_uint64, [c_uint32]),
+    "hsg_hsz_encode": (c_int, [c_int, c_void_p, c_uint64, c_int, c_uint32, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    "hsg_hsz_decode": (c_int, [c_int, c_void_p, c_void_p, c_uint32, c_uint32, c_uint64, c_int,
+                               c_uint32, c_void_p, c_void_p, c_void_p]),
+}
+
+
 def _load_hsgpu() -> Optional[ctypes.CDLL]:
     global _hsgpu_lib, _hsgpu_error
     if _hsgpu_lib is not None or _hsgpu_error is not None:
@@ -238,111 +333,10 @@ def _load_hsgpu() -> Optional[ctypes.CDLL]:
         except Exception as e:  # noqa: BLE001
             _hsgpu_error = f"{type(e).__name__}: {e}"
             return None
-        _declare(lib, "hsg_last_error", c_char_p, [])
-        _declare(lib, "hsg_device_count", c_int, [])
-        _declare(lib, "hsg_pci_location", c_int,
-                 [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
-        _declare(lib, "hsg_pinned_acquire", c_void_p, [c_uint64])
-        _declare(lib, "hsg_pinned_release", c_int, [c_void_p])
-        _declare(lib, "hsg_pinned_acquire_on", c_void_p, [c_uint64, c_int])
-        _declare(lib, "hsg_pinned_stats", None, [ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64)])
-        _declare(lib, "hsg_pinned_trim", c_uint64, [])
-        _declare(lib, "hsg_pinned_set_limit", None, [c_uint64])
+        _declare(lib, HSGPU_ABI)
         from .. import knobs
 
         lib.hsg_pinned_set_limit(knobs.pinned_pool_max_bytes())
-        _declare(lib, "hsg_memcpy", c_int,
-                 [c_int, c_int, c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_int, c_int])
-        _declare(lib, "hsg_stream_join", c_int, [c_int, c_int, c_void_p])
-        _declare(lib, "hsg_stream_sync", c_int, [c_int, c_int])
-        _declare(lib, "hsg_copy_stream", c_void_p, [c_int, c_int])
-        _declare(lib, "hsg_sync_stream_handle", c_int, [c_void_p])
-        _declare(lib, "hsg_desc_size", c_uint64, [])
-        _declare(lib, "hsg_prewarm_module", c_int, [c_int])
-        _declare(lib, "hsg_copy_workspace_bytes", c_uint64, [c_void_p, c_int])
-        _declare(lib, "hsg_copy_nd", c_int,
-                 [c_int, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_int])
-        _declare(lib, "hsg_fp8_quantize", c_int,
-                 [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p])
-        _declare(lib, "hsg_fp8_dequantize", c_int,
-                 [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p])
-        _declare(lib, "hsg_fp8_hadamard_quantize", c_int,
-                 [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p])
-        _declare(lib, "hsg_fp8_hadamard_dequantize", c_int,
-                 [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p])
-        _declare(lib, "hsg_mx8_quantize", c_int,
-                 [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p])
-        _declare(lib, "hsg_mx8_dequantize", c_int,
-                 [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p])
-        _declare(lib, "hsg_drain_start", c_void_p,
-                 [c_int, c_int, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64),
-                  ctypes.POINTER(c_char_p), c_uint64, c_int, c_int, c_int, c_int,
-                  ctypes.POINTER(c_int)])
-        _declare(lib, "hsg_drain_wait", c_int,
-                 [c_void_p, ctypes.POINTER(c_uint64), ctypes.POINTER(c_uint64), c_char_p,
-                  ctypes.POINTER(ctypes.c_double)])
-        _declare(lib, "hsg_drain_pending", c_int, [c_void_p])
-        _declare(lib, "hsg_drain_boost", None, [c_void_p])
-        P = ctypes.POINTER
-        _declare(lib, "hsg_restore_start", c_void_p,
-                 [c_int, c_int, P(c_char_p), P(c_uint64), P(c_uint64), P(c_int), P(c_uint64),
-                  P(c_uint64), P(c_uint64), P(c_int64), P(c_int), c_void_p, c_int64,
-                  P(c_uint64), c_int, c_void_p, c_uint64, c_uint64, c_uint64, c_int, c_int,
-                  c_uint64, c_int, P(c_int), c_int, P(c_int)])
-        _declare(lib, "hsg_restore_wait", c_int,
-                 [c_void_p, P(c_int), c_char_p, P(ctypes.c_double), P(c_uint64), P(c_uint64)])
-        _declare(lib, "hsg_restore_trim", c_uint64, [c_int, c_uint64])
-        _declare(lib, "hsg_restore_trim_pools", c_uint64, [c_int, c_uint64, c_uint64])
-        _declare(lib, "hsg_restore_pool_bytes", None, [c_int, P(c_uint64)])
-        _declare(lib, "hsg_uncached_bytes", c_uint64, [])
-        _declare(lib, "hsg_poison_idle_pools", c_int, [c_int, c_int])
-        _declare(lib, "hsg_restore_prewarm", c_int,
-                 [c_int, c_uint64, c_uint64, c_uint64, c_int, c_uint64])
-        _declare(lib, "hsg_sdma_h2d_submit", c_int,
-                 [c_int, c_void_p, c_void_p, c_uint64, P(c_uint64)])
-        _declare(lib, "hsg_is_managed", c_int, [c_void_p])
-        _declare(lib, "hsg_managed_location", c_int,
-                 [c_void_p, c_uint64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
-        _declare(lib, "hsg_managed_place", c_int, [c_int, c_void_p, c_uint64, c_int, c_void_p])
-        _declare(lib, "hsg_managed_alloc", c_void_p, [c_int, c_uint64])
-        _declare(lib, "hsg_managed_free", c_int, [c_void_p])
-        _declare(lib, "hsg_gate_supported", c_int, [c_int])
-        _declare(lib, "hsg_gate_arm", c_int, [c_int, c_void_p, ctypes.POINTER(ctypes.c_uint32)])
-        _declare(lib, "hsg_gate_release", c_int, [c_int, ctypes.c_uint32])
-        _declare(lib, "hsg_gate_value", ctypes.c_uint32, [c_int])
-        _declare(lib, "hsg_hsz_last_error", c_char_p, [])
-        _declare(lib, "hsg_set_thread_grid_cap", c_int, [c_int])
-        _declare(lib, "hsg_hash64", c_int, [c_int, c_int, c_int, c_void_p, c_uint64, c_uint64,
-                                             c_int, ctypes.POINTER(c_int)])
-        _declare(lib, "hsg_hash64_result", c_int, [c_int, c_int, c_int, ctypes.POINTER(c_uint64)])
-        _declare(lib, "hsg_hash64_batch", c_int,
-                 [c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_uint64)])
-        _declare(lib, "hsg_sdma_last_error", c_char_p, [])
-        _declare(lib, "hsg_sdma_engines", c_int, [c_int])
-        _declare(lib, "hsg_sdma_h2d", c_int, [c_int, c_void_p, c_void_p, c_uint64])
-        _declare(lib, "hsg_uncached_acquire", c_void_p, [c_int, c_uint64])
-        _declare(lib, "hsg_uncached_release", c_int, [c_void_p])
-        _declare(lib, "hsg_uncached_trim", c_uint64, [])
-        _declare(lib, "hsg_rt_dev_alloc", c_void_p, [c_int, c_uint64, c_int])
-        _declare(lib, "hsg_rt_dev_free", None, [c_void_p])
-        _declare(lib, "hsg_rt_memcpy_d2h", c_int, [c_void_p, c_void_p, c_uint64])
-        _declare(lib, "hsg_rt_last_error", c_char_p, [])
-        _declare(lib, "hsg_rt_set_trace", None, [c_int])
-        _declare(lib, "hsg_rt_vmm_alloc", c_void_p, [c_int, c_uint64, c_int])
-        _declare(lib, "hsg_rt_vmm_free", c_int, [c_void_p])
-        _declare(lib, "hsg_rt_vmm_retired_bytes", c_uint64, [])
-        _declare(lib, "hsg_sdma_d2h", c_int,
-                 [c_int, c_void_p, c_void_p, c_uint64, c_int, c_void_p])
-        _declare(lib, "hsg_sdma_d2h_submit", c_int,
-                 [c_int, c_void_p, c_void_p, c_uint64, c_void_p, ctypes.POINTER(c_uint64)])
-        _declare(lib, "hsg_sdma_wait", c_int, [c_uint64])
-        _declare(lib, "hsg_hsz_meta_bytes", c_uint64, [ctypes.c_uint32])
-        _declare(lib, "hsg_hsz_encode", c_int,
-                 [c_int, c_void_p, c_uint64, c_int, ctypes.c_uint32, c_void_p, c_void_p,
-                  c_void_p, c_void_p])
-        _declare(lib, "hsg_hsz_decode", c_int,
-                 [c_int, c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_uint64, c_int,
-                  ctypes.c_uint32, c_void_p, c_void_p, c_void_p])
         if lib.hsg_desc_size() != COPY_DESC_DTYPE.itemsize:
             _hsgpu_error = (f"CopyDesc layout mismatch: native {lib.hsg_desc_size()} "
                             f"vs python {COPY_DESC_DTYPE.itemsize}")
@@ -874,6 +868,20 @@ def mx8_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch.T
                                   dtype_code(dst.dtype), stream_handle), "hsg_mx8_dequantize")
 
 
+# hsg_drain_start `flags` and the buffers hsg_drain_wait / hsg_restore_wait
+# fill (csrc/hsgpu_abi.h HSG_DRAIN_*, HSG_RESTORE_*, HSG_CODEC_*)
+DRAIN_SYNC = 1
+DRAIN_HASH = 2
+DRAIN_DIRECT = 4
+DRAIN_HASH_LOW_PRIO = 8
+DRAIN_NICE_SHIFT = 8     # flags bits 8..15: nice increment of the drain threads
+DRAIN_PARKED_SHIFT = 16  # flags bits 16..23: parked writers (boost)
+DRAIN_MSG_BYTES = 256
+RESTORE_MSG_BYTES = 320
+CODEC_RAW = 0   # a restore item's stored bytes are its logical bytes
+CODEC_HSZ = 1   # ... or a whole HSZ1 blob
+
+
 class NativeDrain:
     """``hsg_drain_start`` / ``hsg_drain_wait`` (csrc/hsdrain.cpp): device
     byte ranges -> files, entirely in native threads (SDMA copies through
@@ -891,7 +899,7 @@ class NativeDrain:
         self._paths = (c_char_p * max(n, 1))(*[os.fsencode(b[2]) for b in blobs])
         err = c_int(0)
         flags = self.flags(fsync, hash_blobs, direct, hash_high_priority, nice) | \
-            (max(0, min(parked_writers, 255)) << 16)
+            (max(0, min(parked_writers, 255)) << DRAIN_PARKED_SHIFT)
         # boost() (any thread) and wait() (the drain's thread) both use the
         # handle: hsg_drain_wait frees the job, so a boost must never run
         # concurrently with or after it
@@ -905,8 +913,9 @@ class NativeDrain:
     @staticmethod
     def flags(fsync: bool, hash_blobs: bool, direct: bool, hash_high_priority: bool,
               nice: int) -> int:
-        return (1 if fsync else 0) | (2 if hash_blobs else 0) | (4 if direct else 0) | \
-            (0 if hash_high_priority else 8) | (max(0, min(nice, 19)) << 8)
+        return (DRAIN_SYNC if fsync else 0) | (DRAIN_HASH if hash_blobs else 0) | \
+            (DRAIN_DIRECT if direct else 0) | (0 if hash_high_priority else DRAIN_HASH_LOW_PRIO) | \
+            (max(0, min(nice, 19)) << DRAIN_NICE_SHIFT)
 
     def pending(self) -> int:
         return require_gpu_lib().hsg_drain_pending(self._h) if self._h else 0
@@ -926,8 +935,8 @@ class NativeDrain:
         lib = require_gpu_lib()
         sums = (c_uint64 * max(self.n, 1))()
         written = c_uint64(0)
-        msg = ctypes.create_string_buffer(256)
-        st = (ctypes.c_double * len(self.STATS))()
+        msg = ctypes.create_string_buffer(DRAIN_MSG_BYTES)
+        st = (c_double * len(self.STATS))()
         with self._lock:
             h, self._h = self._h, None
         r = lib.hsg_drain_wait(h, sums, ctypes.byref(written), msg, st)
@@ -946,7 +955,7 @@ class NativeRestore:
     native threads: pread into pinned slots, SDMA uploads into uncached
     blocks, GPU decode and ONE region-copy launch per item.
 
-    ``items``: (path, file_lo, nbytes, codec (0 raw / 1 hsz1), logical,
+    ``items``: (path, file_lo, nbytes, codec (CODEC_RAW / CODEC_HSZ), logical,
     direct device address or 0, base_off, descriptor rows (packed
     COPY_DESC_DTYPE array whose ``src`` are offsets)).  ``producers``:
     stream handles the device work is ordered after.  ``hash_items``: per
@@ -1006,8 +1015,8 @@ class NativeRestore:
         ``self.stats``: seconds per phase; ``self.bytes_read``."""
         lib = require_gpu_lib()
         item = c_int(-1)
-        msg = ctypes.create_string_buffer(320)
-        st = (ctypes.c_double * len(self.STATS))()
+        msg = ctypes.create_string_buffer(RESTORE_MSG_BYTES)
+        st = (c_double * len(self.STATS))()
         nread = c_uint64(0)
         sums = (c_uint64 * max(self.n, 1))() if self._hash is not None else None
         h, self._h = self._h, None

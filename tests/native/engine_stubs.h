@@ -1,10 +1,12 @@
-// Controls of the CPU device stubs (engine_stubs.cpp) and the entry points of
+// Controls of the CPU device stubs (engine_stubs.cpp); the entry points of
 // the host engines they stand under (hipsnapshot/csrc/hsrestore.cpp,
-// hsdrain.cpp).
+// hsdrain.cpp) and the hooks the stubs define come from the library's header.
 #pragma once
 
 #include <atomic>
 #include <cstdint>
+
+#include "hsgpu_hooks.h"
 
 namespace stub {
 
@@ -30,28 +32,3 @@ void* new_stream();  // a stream of the caller's (a "producer" of restore destin
 void shutdown();     // joins every stub thread
 
 }  // namespace stub
-
-extern "C" {
-void* hsg_restore_start(int dev, int n, const char* const* paths, const uint64_t* file_lo,
-                        const uint64_t* nbytes, const int* codec, const uint64_t* logical,
-                        const uint64_t* direct, const uint64_t* base_off, const int64_t* desc_off,
-                        const int* desc_n, const void* descs, int64_t n_descs,
-                        const uint64_t* producers, int n_producers, uint32_t* err_words,
-                        uint64_t slot_bytes, uint64_t first_bytes, uint64_t piece_bytes,
-                        int nslots, int nreaders, uint64_t budget, int engine,
-                        const int* hash_items, int hash_grid, int* err);
-int hsg_restore_wait(void* handle, int* err_item, char* msg, double* stats,
-                     uint64_t* bytes_read, uint64_t* sums);
-int hsg_restore_prewarm(int dev, uint64_t up_bytes, uint64_t sc_bytes, uint64_t slot_bytes,
-                        int nslots, uint64_t table_bytes);
-uint64_t hsg_restore_trim(int dev, uint64_t keep);
-
-void* hsg_drain_start(int dev, int n, const uint64_t* srcs, const uint64_t* sizes,
-                      const char* const* paths, uint64_t slot_bytes, int nslots, int nwriters,
-                      int flags, int max_hash_grid, int* err);
-void hsg_drain_boost(void* handle);
-int hsg_drain_wait(void* handle, uint64_t* sums, uint64_t* bytes_written, char* msg,
-                   double* stats);
-int hsg_drain_pending(void* handle);
-
-}

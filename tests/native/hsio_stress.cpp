@@ -11,22 +11,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" {
-void* hsio_create(int);
-void hsio_destroy(void*);
-int hsio_eventfd(void*);
-int64_t hsio_submit_write(void*, const char*, const void*, uint64_t, uint64_t, int);
-int64_t hsio_submit_read(void*, const char*, void*, uint64_t, uint64_t, int);
-int hsio_poll(void*, int64_t*, int64_t*, int);
-int64_t hsio_write_sync(void*, const char*, const void*, uint64_t, uint64_t, int);
-int64_t hsio_read_sync(void*, const char*, void*, uint64_t, uint64_t, int);
-void hsio_parallel_memcpy(void*, const void*, uint64_t, int);
-void hsio_set_read_split(void*, uint64_t);
-uint64_t hsz_max_encoded_bytes(uint64_t, uint32_t);
-int64_t hsz_encode_cpu(const void*, uint64_t, int, uint32_t, void*, int);
-int hsz_decode_cpu(const void*, const uint64_t*, uint32_t, uint32_t, uint64_t, int, uint32_t,
-                   void*, int);
-}
+#include "hsio_abi.h"
 
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp/hsio_stress";

@@ -15,6 +15,7 @@ import pytest
 pytestmark = pytest.mark.slow
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "hipsnapshot", "csrc")  # the ABI headers
 SRC = [os.path.join(ROOT, "hipsnapshot", "csrc", "hsio.cpp"),
        os.path.join(ROOT, "hipsnapshot", "csrc", "hsz_cpu.cpp"),
        os.path.join(ROOT, "tests", "native", "hsio_stress.cpp")]
@@ -27,7 +28,7 @@ def test_hsio_under_sanitizer(tmp_path, san):
         pytest.skip("no C++ compiler")
     exe = str(tmp_path / "stress")
     cmd = [cxx, "-std=c++17", "-O1", "-g", f"-fsanitize={san}", "-fno-omit-frame-pointer",
-           "-pthread", "-o", exe] + SRC
+           "-pthread", "-I", CSRC, "-o", exe] + SRC
     proc = subprocess.run(cmd, capture_output=True, text=True)
     if proc.returncode != 0:
         pytest.skip(f"sanitizer toolchain unavailable: {proc.stderr[-300:]}")
@@ -76,8 +77,8 @@ def _build_engine_stress(tmp_path, san, sources=None):
         pytest.skip("no C++ compiler")
     exe = str(tmp_path / f"engine_{san.replace(',', '_') or 'plain'}")
     flags = [f"-fsanitize={san}", "-fno-omit-frame-pointer"] if san else []
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-pthread", "-I",
-           os.path.join(ROOT, "tests", "native")] + flags + ["-o", exe] + (sources or ENGINE_SRC)
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-pthread", "-I", os.path.join(ROOT, "tests", "native"),
+           "-I", CSRC] + flags + ["-o", exe] + (sources or ENGINE_SRC)
     proc = subprocess.run(cmd, capture_output=True, text=True)
     if proc.returncode != 0:
         if san:
