@@ -9,10 +9,12 @@ torch headers and travel with the repository snapshot to the GPU box.
 
 from __future__ import annotations
 
+import concurrent.futures
 import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
@@ -22,13 +24,17 @@ HSGPU_SO = os.path.join(PKG_DIR, "_hsgpu.so")
 # includes hsgpu_abi.h); an exported definition without a prototype is an
 # error, so a signature cannot change without its header.
 HSIO_HDRS = [os.path.join(CSRC, "hsio_abi.h")]
-HSGPU_HDRS = [os.path.join(CSRC, "hsgpu_abi.h"), os.path.join(CSRC, "hsgpu_hooks.h")]
+HSGPU_HDRS = [os.path.join(CSRC, "hsgpu_abi.h"), os.path.join(CSRC, "hsgpu_hooks.h"),
+              os.path.join(CSRC, "hsgpu_common.h")]  # the last one: internal, no ABI
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # The kernels use gfx950-only builtins (MFMA 32x32x16 bf16, fp8 conversions):
 # build for gfx950 whatever else PYTORCH_ROCM_ARCH lists (ROCm images often
 # start that list with older targets).  ``python -m
 # hipsnapshot._build --arch gfx950`` names the target explicitly.
 SUPPORTED_ARCHS = ("gfx950",)
+# compiler processes at a time: a fixed bound, not the CPU count of the host
+# (build hosts are shared and report far more CPUs than a job may use)
+MAX_COMPILE_JOBS = 16
 
 
 def gpu_archs(override: str = "") -> list:
@@ -63,6 +69,13 @@ def _atomic_build(out: str, cmd_for) -> None:
     os.replace(tmp, out)
 
 
+def _compile_objects(compile_cmd, srcs, objdir: str) -> list:
+    objs = [os.path.join(objdir, os.path.basename(s) + ".o") for s in srcs]
+    with concurrent.futures.ThreadPoolExecutor(min(MAX_COMPILE_JOBS, len(srcs))) as pool:
+        list(pool.map(lambda so: _run(compile_cmd + ["-c", so[0], "-o", so[1]]), zip(srcs, objs)))
+    return objs
+
+
 def _missing_prototype_flag(cxx: str) -> str:
     # g++ spells it -Wmissing-declarations; clang has that name for something
     # else and checks functions under -Wmissing-prototypes
@@ -84,19 +97,22 @@ def build_hsio(force: bool = False) -> str:
 def build_hsgpu(force: bool = False, arch: str = "") -> str:
     # hsdrain.cpp / hsrestore.cpp are host-only engines (their HIP calls sit
     # in hshost.hip); hipcc builds them as plain C++ into the same library
-    srcs = [os.path.join(CSRC, "hsgpu.hip"), os.path.join(CSRC, "hsz.hip"),
-            os.path.join(CSRC, "hsdma.hip"), os.path.join(CSRC, "hshost.hip"),
-            os.path.join(CSRC, "hsdrain.cpp"), os.path.join(CSRC, "hsrestore.cpp")]
+    srcs = [os.path.join(CSRC, name) for name in (
+        "hsgpu.hip", "hscopy.hip", "hsquant.hip", "hshash.hip", "hsz.hip", "hsdma.hip",
+        "hshost.hip", "hsdrain.cpp", "hsrestore.cpp")]
     if force or _stale(HSGPU_SO, srcs + HSGPU_HDRS):
         hipcc = os.path.join(ROCM, "bin", "hipcc")
         if not os.path.exists(hipcc):
             hipcc = shutil.which("hipcc") or hipcc
         archs = [f"--offload-arch={a}" for a in gpu_archs(arch)]
-        _atomic_build(HSGPU_SO, lambda out: [hipcc] + archs + ["-O3", "-std=c++17", "-fPIC",
-                                                               "-shared", "-Wall",
-                                                               "-Werror=missing-prototypes",
-                                                               "-o", out]
-                      + srcs + ["-ldl"])
+        compile_cmd = [hipcc] + archs + ["-O3", "-std=c++17", "-fPIC", "-Wall",
+                                         "-Werror=missing-prototypes"]
+        # one object per source, compiled side by side, then one link: every
+        # .hip file parses hip_runtime.h and builds its own code object
+        with tempfile.TemporaryDirectory(prefix="hsgpu_build_") as objdir:
+            objs = _compile_objects(compile_cmd, srcs, objdir)
+            _atomic_build(HSGPU_SO, lambda out: [hipcc] + archs + ["-shared", "-o", out] + objs
+                          + ["-ldl"])
     return HSGPU_SO
 
 

@@ -1,6 +1,6 @@
 // hs64: the blob checksum of hipsnapshot snapshots (host side).
 //
-// Definition (also implemented by the gfx950 kernel `hs_hash64` in hsgpu.hip
+// Definition (also implemented by the gfx950 kernel `hs_hash64` in hshash.hip
 // and by the NumPy reference in hipsnapshot/ops/checksum.py):
 //
 //   words w_i = little-endian uint64 of bytes [8i, 8i+8), the last one

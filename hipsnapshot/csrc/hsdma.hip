@@ -34,7 +34,7 @@
 #include <mutex>
 #include <vector>
 
-#include "hsgpu_hooks.h"
+#include "hsgpu_common.h"
 
 namespace {
 
@@ -63,7 +63,8 @@ std::once_flag g_once;
 HsaApi g_api;
 std::mutex g_mu;
 std::vector<DevInfo> g_devs;
-char g_err[256];
+// why load_api failed: it runs once, so the text is kept for every later caller
+const char* g_api_err = "";
 
 template <typename F>
 bool bind(void* h, const char* name, F* out) {
@@ -75,7 +76,7 @@ void load_api() {
   void* h = dlopen("libhsa-runtime64.so.1", RTLD_NOW | RTLD_NOLOAD);
   if (!h) h = dlopen("libhsa-runtime64.so", RTLD_NOW | RTLD_NOLOAD);
   if (!h) {
-    snprintf(g_err, sizeof(g_err), "libhsa-runtime64 is not loaded in this process");
+    g_api_err = "libhsa-runtime64 is not loaded in this process";
     return;
   }
   HsaApi a;
@@ -88,7 +89,7 @@ void load_api() {
          bind(h, "hsa_amd_memory_async_copy", &a.async_copy) &&
          bind(h, "hsa_amd_memory_async_copy_on_engine", &a.async_copy_on_engine) &&
          bind(h, "hsa_amd_memory_copy_engine_status", &a.engine_status);
-  if (!a.ok) snprintf(g_err, sizeof(g_err), "libhsa-runtime64 lacks the async copy API");
+  if (!a.ok) g_api_err = "libhsa-runtime64 lacks the async copy API";
   g_api = a;
 }
 
@@ -109,11 +110,19 @@ hsa_status_t scan_agent(hsa_agent_t a, void* data) {
 
 // The HSA agent of HIP device `dev`, matched by PCI bus/device (HIP may hide
 // devices through HIP_VISIBLE_DEVICES, so the indices need not agree).
+// Null with the caller's error message set; a device that did not match is
+// looked up again by the next call (only the API binding's failure is kept).
 DevInfo* dev_info(int dev) {
   std::call_once(g_once, load_api);
-  if (!g_api.ok) return nullptr;
+  if (!g_api.ok) {
+    hs_set_error("%s", g_api_err);
+    return nullptr;
+  }
   std::lock_guard<std::mutex> g(g_mu);
-  if (dev < 0) return nullptr;
+  if (dev < 0) {
+    hs_set_error("no HSA agent for device %d", dev);
+    return nullptr;
+  }
   if (int(g_devs.size()) <= dev) g_devs.resize(dev + 1);
   DevInfo& d = g_devs[dev];
   if (d.ok) return &d;
@@ -121,13 +130,13 @@ DevInfo* dev_info(int dev) {
   if (hipDeviceGetAttribute(&bus, hipDeviceAttributePciBusId, dev) != hipSuccess ||
       hipDeviceGetAttribute(&devno, hipDeviceAttributePciDeviceId, dev) != hipSuccess ||
       hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainId, dev) != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "hipDeviceGetAttribute(PCI) failed for device %d", dev);
+    hs_set_error("hipDeviceGetAttribute(PCI) failed for device %d", dev);
     return nullptr;
   }
   AgentScan scan;
   g_api.iterate_agents(scan_agent, &scan);
   if (scan.cpus.empty()) {
-    snprintf(g_err, sizeof(g_err), "no HSA CPU agent");
+    hs_set_error("no HSA CPU agent");
     return nullptr;
   }
   for (hsa_agent_t a : scan.gpus) {
@@ -151,8 +160,7 @@ DevInfo* dev_info(int dev) {
       return &d;
     }
   }
-  snprintf(g_err, sizeof(g_err), "no HSA GPU agent matches HIP device %d (bus %d dev %d)", dev,
-           bus, devno);
+  hs_set_error("no HSA GPU agent matches HIP device %d (bus %d dev %d)", dev, bus, devno);
   return nullptr;
 }
 
@@ -165,7 +173,10 @@ hsa_signal_t take_signal() {
     return s;
   }
   hsa_signal_t s{0};
-  if (g_api.signal_create(1, 0, nullptr, &s) != HSA_STATUS_SUCCESS) s.handle = 0;
+  if (g_api.signal_create(1, 0, nullptr, &s) != HSA_STATUS_SUCCESS) {
+    hs_set_error("hsa_signal_create failed");
+    s.handle = 0;
+  }
   return s;
 }
 
@@ -174,11 +185,33 @@ void give_signal(hsa_signal_t s) {
   else g_api.signal_destroy(s);
 }
 
+// One system-scope release on `stream`, waited for: the producer's work is
+// done AND written back to system scope before an SDMA engine reads it.
+int release_to_system(int dev, void* stream) {
+  hipError_t e = hipSetDevice(dev);
+  if (e != hipSuccess) {
+    hs_set_error("hipSetDevice(%d): %s", dev, hipGetErrorString(e));
+    return -2;
+  }
+  hipEvent_t ev;
+  e = hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem);
+  if (e != hipSuccess) {
+    hs_set_error("release event: %s", hipGetErrorString(e));
+    return -3;
+  }
+  e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+  if (e == hipSuccess) e = hipEventSynchronize(ev);
+  (void)hipEventDestroy(ev);
+  if (e != hipSuccess) {
+    hs_set_error("release event: %s", hipGetErrorString(e));
+    return -4;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
-
-const char* hsg_sdma_last_error() { return g_err; }
 
 // Number of SDMA engines usable for device -> host copies of `dev` (0: the
 // SDMA path is unavailable; callers use hipMemcpyAsync).
@@ -197,22 +230,7 @@ int hsg_sdma_d2h(int dev, void* dst, const void* src, uint64_t n, int max_engine
   DevInfo* d = dev_info(dev);
   if (!d) return -1;
   if (n == 0) return 0;
-  hipError_t e = hipSetDevice(dev);
-  if (e != hipSuccess) return -2;
-  {
-    // producer work done AND written back to system scope before SDMA reads
-    hipEvent_t ev;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem) !=
-        hipSuccess)
-      return -3;
-    e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = hipEventSynchronize(ev);
-    hipEventDestroy(ev);
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "release event: %s", hipGetErrorString(e));
-      return -4;
-    }
-  }
+  if (const int r = release_to_system(dev, stream)) return r;
   // max_engines 0: one request, ROCr picks the engine (it spreads concurrent
   // requests from several staging threads over its engines and never
   // conflicts with copies the HIP runtime issues itself); > 0: split over
@@ -250,7 +268,7 @@ int hsg_sdma_d2h(int dev, void* dst, const void* src, uint64_t n, int max_engine
       st = g_api.async_copy(dp, d->cpu, sp, d->gpu, len, 0, nullptr, s);
     if (st != HSA_STATUS_SUCCESS) {
       give_signal(s);
-      snprintf(g_err, sizeof(g_err), "hsa_amd_memory_async_copy: status 0x%x", unsigned(st));
+      hs_set_error("hsa_amd_memory_async_copy: status 0x%x", unsigned(st));
       rc = -6;
       break;
     }
@@ -260,7 +278,7 @@ int hsg_sdma_d2h(int dev, void* dst, const void* src, uint64_t n, int max_engine
     const hsa_signal_value_t v =
         g_api.signal_wait(s, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED);
     if (v < 0 && rc == 0) {
-      snprintf(g_err, sizeof(g_err), "SDMA copy reported an error (%ld)", long(v));
+      hs_set_error("SDMA copy reported an error (%ld)", long(v));
       rc = -7;
     }
     give_signal(s);
@@ -280,28 +298,14 @@ int hsg_sdma_d2h_submit(int dev, void* dst, const void* src, uint64_t n, void* s
   DevInfo* d = dev_info(dev);
   if (!d) return -1;
   if (n == 0) return 0;
-  hipError_t e = hipSetDevice(dev);
-  if (e != hipSuccess) return -2;
-  {
-    hipEvent_t ev;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem) !=
-        hipSuccess)
-      return -3;
-    e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = hipEventSynchronize(ev);
-    hipEventDestroy(ev);
-    if (e != hipSuccess) {
-      snprintf(g_err, sizeof(g_err), "release event: %s", hipGetErrorString(e));
-      return -4;
-    }
-  }
+  if (const int r = release_to_system(dev, stream)) return r;
   hsa_signal_t s = take_signal();
   if (s.handle == 0) return -5;
   g_api.signal_store(s, 1);
   const hsa_status_t st = g_api.async_copy(dst, d->cpu, src, d->gpu, n, 0, nullptr, s);
   if (st != HSA_STATUS_SUCCESS) {
     give_signal(s);
-    snprintf(g_err, sizeof(g_err), "hsa_amd_memory_async_copy: status 0x%x", unsigned(st));
+    hs_set_error("hsa_amd_memory_async_copy: status 0x%x", unsigned(st));
     return -6;
   }
   *handle = s.handle;
@@ -313,20 +317,7 @@ int hsg_sdma_d2h_submit(int dev, void* dst, const void* src, uint64_t n, void* s
 // async-take drain of a frozen arena.  Per-copy release events (above) cost
 // an event create/record/sync/destroy each -- ~1.3 ms per 32 MiB chunk when
 // the trainer's launches contend for the same runtime (profiles/r3/s2/overlap).
-int hsg_sdma_release(int dev, void* stream) {
-  if (hipSetDevice(dev) != hipSuccess) return -2;
-  hipEvent_t ev;
-  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess)
-    return -3;
-  hipError_t e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
-  if (e == hipSuccess) e = hipEventSynchronize(ev);
-  hipEventDestroy(ev);
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "release event: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
+int hsg_sdma_release(int dev, void* stream) { return release_to_system(dev, stream); }
 
 // hsg_sdma_d2h_submit without the per-copy release (after hsg_sdma_release).
 int hsg_sdma_d2h_submit_released(int dev, void* dst, const void* src, uint64_t n,
@@ -341,7 +332,7 @@ int hsg_sdma_d2h_submit_released(int dev, void* dst, const void* src, uint64_t n
   const hsa_status_t st = g_api.async_copy(dst, d->cpu, src, d->gpu, n, 0, nullptr, s);
   if (st != HSA_STATUS_SUCCESS) {
     give_signal(s);
-    snprintf(g_err, sizeof(g_err), "hsa_amd_memory_async_copy: status 0x%x", unsigned(st));
+    hs_set_error("hsa_amd_memory_async_copy: status 0x%x", unsigned(st));
     return -6;
   }
   *handle = s.handle;
@@ -372,14 +363,14 @@ int hsg_sdma_h2d(int dev, void* dst, const void* src, uint64_t n) {
   const hsa_status_t st = g_api.async_copy(dst, d->gpu, src, d->cpu, n, 0, nullptr, s);
   if (st != HSA_STATUS_SUCCESS) {
     give_signal(s);
-    snprintf(g_err, sizeof(g_err), "hsa_amd_memory_async_copy (h2d): status 0x%x", unsigned(st));
+    hs_set_error("hsa_amd_memory_async_copy (h2d): status 0x%x", unsigned(st));
     return -6;
   }
   const hsa_signal_value_t v =
       g_api.signal_wait(s, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED);
   give_signal(s);
   if (v < 0) {
-    snprintf(g_err, sizeof(g_err), "SDMA h2d copy reported an error (%ld)", long(v));
+    hs_set_error("SDMA h2d copy reported an error (%ld)", long(v));
     return -7;
   }
   return 0;
@@ -416,7 +407,7 @@ int hsg_sdma_h2d_submit_on(int dev, void* dst, const void* src, uint64_t n, int 
                   : g_api.async_copy(dst, d->gpu, src, d->cpu, n, 0, nullptr, s);
   if (st != HSA_STATUS_SUCCESS) {
     give_signal(s);
-    snprintf(g_err, sizeof(g_err), "hsa_amd_memory_async_copy (h2d): status 0x%x", unsigned(st));
+    hs_set_error("hsa_amd_memory_async_copy (h2d): status 0x%x", unsigned(st));
     return -6;
   }
   *handle = s.handle;
@@ -433,7 +424,7 @@ int hsg_sdma_wait(uint64_t handle) {
       g_api.signal_wait(s, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED);
   give_signal(s);
   if (v < 0) {
-    snprintf(g_err, sizeof(g_err), "SDMA copy reported an error (%ld)", long(v));
+    hs_set_error("SDMA copy reported an error (%ld)", long(v));
     return -7;
   }
   return 0;

@@ -39,8 +39,11 @@ enum {
 extern "C" {
 #endif
 
-// hsgpu.hip: devices, pinned host pool
+// hsgpu.hip: the message of the calling thread's last failed hsg_* call (the
+// library's only error channel: every failing entry point sets it)
 const char* hsg_last_error();
+
+// hsgpu.hip: devices, pinned host pool
 int hsg_device_count();
 int hsg_pci_location(int dev, int* domain, int* bus, int* device);
 void* hsg_pinned_acquire(uint64_t nbytes);
@@ -65,19 +68,21 @@ int hsg_stream_sync(int dev, int slot);
 void* hsg_copy_stream(int dev, int slot);
 int hsg_sync_stream_handle(void* stream);
 int hsg_set_thread_grid_cap(int cap);
-uint64_t hsg_desc_size();
 int hsg_prewarm_module(int dev);
+
+// hscopy.hip: batched strided copy / cast
+uint64_t hsg_desc_size();
 uint64_t hsg_copy_workspace_bytes(const void* descs, int n);
 int hsg_copy_nd(int dev, const void* descs, int n, void* workspace, uint64_t ws_bytes,
                 void* pinned_stage, void* stream, int sync);
 
-// hsgpu.hip: hs64 checksum
+// hshash.hip: hs64 checksum
 int hsg_hash64(int dev, int slot, int after_slot, const void* p, uint64_t n, uint64_t first_word,
                int max_grid, int* handle);
 int hsg_hash64_result(int dev, int slot, int handle, uint64_t* out);
 int hsg_hash64_batch(int dev, void* stream, const void* descs, int n, uint64_t* sums_out);
 
-// hsgpu.hip: fp8 / MX8 quantization
+// hsquant.hip: fp8 / MX8 quantization
 int hsg_fp8_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out, void* scales,
                      int vpt, void* stream);
 int hsg_fp8_dequantize(int dev, const void* q, const void* scales, int64_t n, void* dst,
@@ -103,7 +108,6 @@ int hsg_gate_release(int dev, uint32_t value);
 uint32_t hsg_gate_value(int dev);
 
 // hsz.hip: HSZ1 GPU codec
-const char* hsg_hsz_last_error();
 uint64_t hsg_hsz_meta_bytes(uint32_t n_frames);
 int hsg_hsz_encode(int dev, const void* src, uint64_t logical, int w, uint32_t frame_bytes,
                    void* out, void* meta, void* total, void* stream);
@@ -112,7 +116,6 @@ int hsg_hsz_decode(int dev, const void* frames, const void* offsets, uint32_t fi
                    void* stream, void* err);
 
 // hsdma.hip: SDMA copies
-const char* hsg_sdma_last_error();
 int hsg_sdma_engines(int dev);
 int hsg_sdma_d2h(int dev, void* dst, const void* src, uint64_t n, int max_engines, void* stream);
 int hsg_sdma_d2h_submit(int dev, void* dst, const void* src, uint64_t n, void* stream,
@@ -122,7 +125,6 @@ int hsg_sdma_h2d_submit(int dev, void* dst, const void* src, uint64_t n, uint64_
 int hsg_sdma_wait(uint64_t handle);
 
 // hshost.hip: HIP runtime calls of the host engines
-const char* hsg_rt_last_error();
 void hsg_rt_set_trace(int on);
 void* hsg_rt_dev_alloc(int dev, uint64_t nbytes, int uncached);
 void hsg_rt_dev_free(void* p);

@@ -17,6 +17,8 @@ extern "C" {
 // hsgpu.hip
 int hsg_thread_grid_cap();
 int hsg_stream_priority(int dev, int slot, int high);
+
+// hshash.hip
 int hsg_hash64_into(int dev, void* stream, const void* p, uint64_t n, uint64_t first_word,
                     int max_grid, void* acc);
 

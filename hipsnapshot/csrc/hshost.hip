@@ -17,18 +17,14 @@
 #include <mutex>
 #include <unordered_map>
 
-#include "hsgpu_hooks.h"
+#include "hsgpu_common.h"
 
 namespace {
 
-// The last failed runtime call of these hooks, with HIP's error name: the
-// engines' "device work" errors carry it (a bare EIO named nothing).
-std::mutex g_rt_mu;
-char g_rt_err[200] = {0};
-
+// The failed runtime call of a hook, with HIP's error name: the engines'
+// "device work" errors carry it (a bare EIO named nothing).
 void note(const char* what, hipError_t e) {
-  std::lock_guard<std::mutex> g(g_rt_mu);
-  snprintf(g_rt_err, sizeof(g_rt_err), "%s: %s (%d)", what, hipGetErrorName(e), int(e));
+  hs_set_error("%s: %s (%d)", what, hipGetErrorName(e), int(e));
 }
 
 // Pool trace (hsg_rt_set_trace(1), from Python native.set_pool_trace): one
@@ -48,8 +44,6 @@ uint64_t now_us() {
 
 extern "C" {
 
-const char* hsg_rt_last_error() { return g_rt_err; }
-
 int hsg_rt_trace_on() { return trace_on(); }
 
 void hsg_rt_set_trace(int on) { g_trace.store(on ? 1 : 0); }
@@ -60,17 +54,23 @@ void hsg_rt_trace(const char* what, const void* p, uint64_t n, int kind) {
           (unsigned long long)now_us(), what, p, (unsigned long long)n, kind);
 }
 
-int hsg_rt_set_device(int dev) { return hipSetDevice(dev) == hipSuccess ? 0 : -1; }
+int hsg_rt_set_device(int dev) {
+  const hipError_t e = hipSetDevice(dev);
+  if (e == hipSuccess) return 0;
+  note("hipSetDevice", e);
+  return -1;
+}
 
 // `nbytes` of device memory on `dev`: device-uncached (hipDeviceMallocUncached:
 // SDMA upload targets the kernels read without an acquire) or plain.  Null on
 // failure (the error is cleared: callers trim their pools and retry).
 void* hsg_rt_dev_alloc(int dev, uint64_t nbytes, int uncached) {
-  if (hipSetDevice(dev) != hipSuccess) return nullptr;
+  if (hsg_rt_set_device(dev) != 0) return nullptr;
   void* p = nullptr;
   const hipError_t e = uncached ? hipExtMallocWithFlags(&p, nbytes, hipDeviceMallocUncached)
                                 : hipMalloc(&p, nbytes);
   if (e != hipSuccess) {
+    note(uncached ? "hipExtMallocWithFlags" : "hipMalloc", e);
     (void)hipGetLastError();
     return nullptr;
   }
@@ -113,7 +113,7 @@ std::atomic<uint64_t> g_vmm_retired{0};  // bytes of virtual ranges kept reserve
 }  // namespace
 
 void* hsg_rt_vmm_alloc(int dev, uint64_t nbytes, int uncached) {
-  if (hipSetDevice(dev) != hipSuccess) return nullptr;
+  if (hsg_rt_set_device(dev) != 0) return nullptr;
   hipMemAllocationProp prop = {};
   prop.type = uncached ? hipMemAllocationTypeUncached : hipMemAllocationTypePinned;
   prop.location.type = hipMemLocationTypeDevice;
@@ -165,7 +165,10 @@ int hsg_rt_vmm_free(void* p) {
   {
     std::lock_guard<std::mutex> g(g_vmm_mu);
     auto it = g_vmm.find(p);
-    if (it == g_vmm.end()) return -1;
+    if (it == g_vmm.end()) {
+      hs_set_error("hsg_rt_vmm_free: %p is not a block of hsg_rt_vmm_alloc", p);
+      return -1;
+    }
     b = it->second;
     g_vmm.erase(it);
   }
@@ -188,11 +191,15 @@ uint64_t hsg_rt_vmm_retired_bytes() { return g_vmm_retired.load(); }
 // A new event recorded on `stream` (null on failure).
 void* hsg_rt_event_record(void* stream) {
   hipEvent_t ev = nullptr;
-  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+  hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    note("hipEventCreateWithFlags", e);
     (void)hipGetLastError();
     return nullptr;
   }
-  if (hipEventRecord(ev, static_cast<hipStream_t>(stream)) != hipSuccess) {
+  e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) {
+    note("hipEventRecord", e);
     (void)hipGetLastError();
     (void)hipEventDestroy(ev);
     return nullptr;
@@ -220,6 +227,7 @@ int hsg_rt_stream_after(void* waiter, void* producer) {
       hipStreamWaitEvent(static_cast<hipStream_t>(waiter), static_cast<hipEvent_t>(ev), 0);
   hsg_rt_event_free(ev);
   if (e != hipSuccess) {
+    note("hipStreamWaitEvent", e);
     (void)hipGetLastError();
     return -1;
   }
@@ -235,11 +243,11 @@ int hsg_rt_stream_sync(void* stream) {
 
 // Blocking device -> host copy of n bytes (small result arrays).
 int hsg_rt_memcpy_d2h(void* dst, const void* src, uint64_t n) {
-  if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) {
-    (void)hipGetLastError();
-    return -1;
-  }
-  return 0;
+  const hipError_t e = hipMemcpy(dst, src, n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) return 0;
+  note("hipMemcpy", e);
+  (void)hipGetLastError();
+  return -1;
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 //                frame table (kept from its first chunk) and launches the
 //                device work on one of two streams: the HSZ1 decode
 //                (csrc/hsz.hip) straight into the destination or into a
-//                scratch block, then ONE hs_copy_nd launch (csrc/hsgpu.hip)
+//                scratch block, then ONE hs_copy_nd launch (csrc/hscopy.hip)
 //                writing every destination view (strided / narrowed / cast);
 //   retire       waits each blob's completion event and returns its device
 //                blocks, so the HBM the pipeline holds stays within a budget.
@@ -31,7 +31,7 @@
 // (buffer consumers copying into the target tensors).
 //
 // Host code only: every device operation goes through a C hook -- SDMA,
-// decode and copy launches in hsdma.hip / hsz.hip / hsgpu.hip, the HIP
+// decode, hash and copy launches in hsdma.hip / hsz.hip / hshash.hip / hscopy.hip, the HIP
 // runtime calls (device, memory, events, streams) in hshost.hip -- so this
 // engine also builds without HIP, against the stubs of
 // tests/native/engine_stubs.cpp, under ThreadSanitizer and AddressSanitizer
@@ -375,6 +375,9 @@ struct Job {
 
   void add(Stat k, uint64_t t0) { ns[k].fetch_add(now_ns() - t0); }
 
+  // An -EIO names the device hook that failed and carries that hook's message
+  // (hsg_last_error, per thread): call it on the hook's thread, before any
+  // other hook.
   void fail(int code, int item, const char* what) {
     int expected = 0;
     if (err.compare_exchange_strong(expected, code)) {
@@ -383,7 +386,7 @@ struct Job {
       snprintf(errmsg, sizeof(errmsg), "%s %s: %s%s%s", what,
                item >= 0 ? items[item].path.c_str() : "",
                code < 0 && code > -4096 ? strerror(-code) : "error",
-               code == -EIO ? " -- " : "", code == -EIO ? hsg_rt_last_error() : "");
+               code == -EIO ? " -- " : "", code == -EIO ? hsg_last_error() : "");
     }
     cv.notify_all();
   }

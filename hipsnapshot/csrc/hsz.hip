@@ -46,7 +46,7 @@
 #include <cstdlib>
 #include <cstdio>
 
-#include "hsgpu_hooks.h"
+#include "hsgpu_common.h"
 
 namespace {
 
@@ -1469,18 +1469,14 @@ hsz_decode2g(const uint8_t* __restrict__ frames, const uint64_t* __restrict__ of
   if (threadIdx.x < tail_len) o[W * n + threadIdx.x] = escv[n_esc + threadIdx.x];
 }
 
-thread_local char g_hsz_err[256];
-
 int fail(const char* what, hipError_t e) {
-  snprintf(g_hsz_err, sizeof(g_hsz_err), "%s: %s", what, hipGetErrorString(e));
+  hs_set_error("%s: %s", what, hipGetErrorString(e));
   return -static_cast<int>(e) - 1;
 }
 
 }  // namespace
 
 extern "C" {
-
-const char* hsg_hsz_last_error() { return g_hsz_err; }
 
 uint64_t hsg_hsz_meta_bytes(uint32_t n_frames) {
   return uint64_t(n_frames) *
@@ -1495,7 +1491,15 @@ int hsg_hsz_encode(int dev, const void* src, uint64_t logical, int w, uint32_t f
                    void* out, void* meta, void* total, void* stream) {
   hipError_t e = hipSetDevice(dev);
   if (e != hipSuccess) return fail("hipSetDevice", e);
-  if (frame_bytes % 16 || frame_bytes % w) return -1000;
+  if (!(w == 1 || w == 2 || w == 4 || w == 8)) {
+    hs_set_error("hsz encode: unsupported element width %d", w);
+    return -1001;
+  }
+  if (frame_bytes % 16 || frame_bytes % w) {
+    hs_set_error("hsz encode: frame of %u bytes is no multiple of 16 and of the width %d",
+                 frame_bytes, w);
+    return -1000;
+  }
   const uint32_t nf = logical ? uint32_t((logical + frame_bytes - 1) / frame_bytes) : 1;
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto* src8 = static_cast<const uint8_t*>(src);
@@ -1509,8 +1513,7 @@ int hsg_hsz_encode(int dev, const void* src, uint64_t logical, int w, uint32_t f
     case 1: hipLaunchKernelGGL(hsz_analyze<1>, dim3(g), dim3(kThreads), 0, s, src8, logical, frame_bytes, m, lanes, pbits, nf); break;
     case 2: hipLaunchKernelGGL(hsz_analyze<2>, dim3(g), dim3(kThreads), 0, s, src8, logical, frame_bytes, m, lanes, pbits, nf); break;
     case 4: hipLaunchKernelGGL(hsz_analyze<4>, dim3(g), dim3(kThreads), 0, s, src8, logical, frame_bytes, m, lanes, pbits, nf); break;
-    case 8: hipLaunchKernelGGL(hsz_analyze<8>, dim3(g), dim3(kThreads), 0, s, src8, logical, frame_bytes, m, lanes, pbits, nf); break;
-    default: return -1001;
+    default: hipLaunchKernelGGL(hsz_analyze<8>, dim3(g), dim3(kThreads), 0, s, src8, logical, frame_bytes, m, lanes, pbits, nf); break;
   }
   hipLaunchKernelGGL(hsz_layout, dim3(1), dim3(1024), 0, s, m, nf, o, logical, uint32_t(w),
                      frame_bytes, static_cast<uint64_t*>(total));
@@ -1547,6 +1550,10 @@ int hsg_hsz_decode(int dev, const void* frames, const void* offsets, uint32_t fi
   hipError_t e = hipSetDevice(dev);
   if (e != hipSuccess) return fail("hipSetDevice", e);
   if (count == 0) return 0;
+  if (!(w == 1 || w == 2 || w == 4 || w == 8)) {
+    hs_set_error("hsz decode: unsupported element width %d", w);
+    return -1001;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto* fr = static_cast<const uint8_t*>(frames);
   auto* off = static_cast<const uint64_t*>(offsets);
@@ -1556,8 +1563,7 @@ int hsg_hsz_decode(int dev, const void* frames, const void* offsets, uint32_t fi
     case 1: hipLaunchKernelGGL(hsz_decode<1>, dim3(count), dim3(kThreads), 0, s, fr, off, first, logical, frame_bytes, o, ew); break;
     case 2: hipLaunchKernelGGL(hsz_decode<2>, dim3(count), dim3(kThreads), 0, s, fr, off, first, logical, frame_bytes, o, ew); break;
     case 4: hipLaunchKernelGGL(hsz_decode<4>, dim3(count), dim3(kThreads), 0, s, fr, off, first, logical, frame_bytes, o, ew); break;
-    case 8: hipLaunchKernelGGL(hsz_decode<8>, dim3(count), dim3(kThreads), 0, s, fr, off, first, logical, frame_bytes, o, ew); break;
-    default: return -1001;
+    default: hipLaunchKernelGGL(hsz_decode<8>, dim3(count), dim3(kThreads), 0, s, fr, off, first, logical, frame_bytes, o, ew); break;
   }
   if (w == 2)
     hipLaunchKernelGGL((hsz_decode2g<2, 8>), dim3(count), dim3(kThreads), 0, s, fr, off, first,

@@ -2,7 +2,7 @@
 
 Not in the reference.  ``Snapshot.take(path, app_state, base=B)`` hashes every
 eligible leaf tensor of the take where it lives -- HBM leaves of a device by
-ONE ``hs_hash64_batch`` launch (csrc/hsgpu.hip), host leaves by the C++ hasher
+ONE ``hs_hash64_batch`` launch (csrc/hshash.hip), host leaves by the C++ hasher
 -- *before* anything is staged, and compares each digest with the one the base
 recorded for the same leaf.  A leaf whose digest, byte count, dtype and shape
 all match is neither staged, copied nor written: its manifest entry points at

@@ -288,12 +288,10 @@ HSGPU_ABI = {
     "hsg_gate_arm": (c_int, [c_int, c_void_p, P(c_uint32)]),
     "hsg_gate_release": (c_int, [c_int, c_uint32]),
     "hsg_gate_value": (c_uint32, [c_int]),
-    "hsg_hsz_last_error": (c_char_p, []),
     "hsg_set_thread_grid_cap": (c_int, [c_int]),
     "hsg_hash64": (c_int, [c_int, c_int, c_int, c_void_p, c_uint64, c_uint64, c_int, P(c_int)]),
     "hsg_hash64_result": (c_int, [c_int, c_int, c_int, P(c_uint64)]),
     "hsg_hash64_batch": (c_int, [c_int, c_void_p, c_void_p, c_int, P(c_uint64)]),
-    "hsg_sdma_last_error": (c_char_p, []),
     "hsg_sdma_engines": (c_int, [c_int]),
     "hsg_sdma_h2d": (c_int, [c_int, c_void_p, c_void_p, c_uint64]),
     "hsg_uncached_acquire": (c_void_p, [c_int, c_uint64]),
@@ -302,7 +300,6 @@ HSGPU_ABI = {
     "hsg_rt_dev_alloc": (c_void_p, [c_int, c_uint64, c_int]),
     "hsg_rt_dev_free": (None, [c_void_p]),
     "hsg_rt_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_uint64]),
-    "hsg_rt_last_error": (c_char_p, []),
     "hsg_rt_set_trace": (None, [c_int]),
     "hsg_rt_vmm_alloc": (c_void_p, [c_int, c_uint64, c_int]),
     "hsg_rt_vmm_free": (c_int, [c_void_p]),
@@ -496,22 +493,15 @@ def sdma_d2h(dev: int, dst: int, src: int, nbytes: int, stream=None,
     """Blocking device -> pinned-host copy on the SDMA engines, ordered after
     the work queued on ``stream`` (handle or torch stream; None/0 = the null
     stream).  ``max_engines`` 0 = every free engine."""
-    lib = require_gpu_lib()
-    r = lib.hsg_sdma_d2h(dev, dst, src, nbytes, max_engines, _stream_handle(stream) or None)
-    if r != 0:
-        msg = lib.hsg_sdma_last_error()
-        raise HipError(f"hsg_sdma_d2h failed ({r}): {msg.decode() if msg else ''}")
+    _check(require_gpu_lib().hsg_sdma_d2h(dev, dst, src, nbytes, max_engines,
+                                          _stream_handle(stream) or None), "hsg_sdma_d2h")
 
 
 def sdma_h2d(dev: int, dst: int, src: int, nbytes: int) -> None:
     """Blocking pinned-host -> device copy on an SDMA engine.  ``dst`` must be
     an ``UncachedBlock`` (the GPU reads it without an L2, so the copy needs no
     acquire before kernels read it)."""
-    lib = require_gpu_lib()
-    r = lib.hsg_sdma_h2d(dev, dst, src, nbytes)
-    if r != 0:
-        msg = lib.hsg_sdma_last_error()
-        raise HipError(f"hsg_sdma_h2d failed ({r}): {msg.decode() if msg else ''}")
+    _check(require_gpu_lib().hsg_sdma_h2d(dev, dst, src, nbytes), "hsg_sdma_h2d")
 
 
 class UncachedBlock:
@@ -550,22 +540,15 @@ def uncached_trim() -> int:
 def sdma_d2h_submit(dev: int, dst: int, src: int, nbytes: int, stream=None) -> int:
     """Submit one device -> pinned-host SDMA copy ordered after ``stream``;
     returns the handle ``sdma_wait`` takes (exactly once)."""
-    lib = require_gpu_lib()
     h = c_uint64(0)
-    r = lib.hsg_sdma_d2h_submit(dev, dst, src, nbytes, _stream_handle(stream) or None,
-                                ctypes.byref(h))
-    if r != 0:
-        msg = lib.hsg_sdma_last_error()
-        raise HipError(f"hsg_sdma_d2h_submit failed ({r}): {msg.decode() if msg else ''}")
+    _check(require_gpu_lib().hsg_sdma_d2h_submit(dev, dst, src, nbytes,
+                                                 _stream_handle(stream) or None, ctypes.byref(h)),
+           "hsg_sdma_d2h_submit")
     return h.value
 
 
 def sdma_wait(handle: int) -> None:
-    lib = require_gpu_lib()
-    r = lib.hsg_sdma_wait(handle)
-    if r != 0:
-        msg = lib.hsg_sdma_last_error()
-        raise HipError(f"hsg_sdma_wait failed ({r}): {msg.decode() if msg else ''}")
+    _check(require_gpu_lib().hsg_sdma_wait(handle), "hsg_sdma_wait")
 
 
 def copy_stream(dev: int, slot: int) -> int:
@@ -824,7 +807,7 @@ def fp8_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch.T
 
 def fp8_hadamard_quantize(dev: int, src: torch.Tensor, out: torch.Tensor, scales: torch.Tensor,
                           stream_handle: int) -> None:
-    """MFMA Hadamard-32 rotation + blockwise e4m3 quantization (see hsgpu.hip)."""
+    """MFMA Hadamard-32 rotation + blockwise e4m3 quantization (see hsquant.hip)."""
     lib = require_gpu_lib()
     n = src.numel()
     n_pad = (n + 31) // 32 * 32
@@ -1184,12 +1167,6 @@ def hsz_max_encoded_bytes(logical: int, frame_bytes: int) -> int:
     return int(hsio().hsz_max_encoded_bytes(logical, frame_bytes))
 
 
-def _hsz_check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = require_gpu_lib().hsg_hsz_last_error().decode()
-        raise HipError(f"{what} failed ({rc}): {msg}")
-
-
 def hsz_meta_bytes(n_frames: int) -> int:
     return int(require_gpu_lib().hsg_hsz_meta_bytes(n_frames))
 
@@ -1198,9 +1175,9 @@ def hsz_encode_gpu(dev: int, src_addr: int, logical: int, w: int, frame_bytes: i
                    out_addr: int, meta_addr: int, total_addr: int, stream_handle: int) -> None:
     """Enqueue the 3 encode kernels on ``stream_handle`` (no synchronisation)."""
     assert src_addr % 16 == 0 and out_addr % 16 == 0, "HSZ1 buffers must be 16-B aligned"
-    _hsz_check(require_gpu_lib().hsg_hsz_encode(dev, src_addr, logical, w, frame_bytes,
-                                                out_addr, meta_addr, total_addr, stream_handle),
-               "hsg_hsz_encode")
+    _check(require_gpu_lib().hsg_hsz_encode(dev, src_addr, logical, w, frame_bytes,
+                                            out_addr, meta_addr, total_addr, stream_handle),
+           "hsg_hsz_encode")
 
 
 def hsz_decode_gpu(dev: int, frames_addr: int, offsets_addr: int, first: int, count: int,
@@ -1209,10 +1186,10 @@ def hsz_decode_gpu(dev: int, frames_addr: int, offsets_addr: int, first: int, co
     """Enqueue the decode of frames [first, first+count) on ``stream_handle``.
     ``err_addr``: a zeroed host-mapped pinned uint32 (``DecodeErrorWord``) the
     kernels set to 1 for a rejected frame; check it after the stream sync."""
-    _hsz_check(require_gpu_lib().hsg_hsz_decode(dev, frames_addr, offsets_addr, first, count,
-                                                logical, w, frame_bytes, out_addr,
-                                                stream_handle, err_addr or None),
-               "hsg_hsz_decode")
+    _check(require_gpu_lib().hsg_hsz_decode(dev, frames_addr, offsets_addr, first, count,
+                                            logical, w, frame_bytes, out_addr,
+                                            stream_handle, err_addr or None),
+           "hsg_hsz_decode")
 
 
 class CorruptBlobError(ValueError, RuntimeError):

@@ -145,7 +145,7 @@ def fp8_entry_quant_info(t: torch.Tensor, vpt: int = DEFAULT_VPT,
 def _scale_and_quant(blocks: torch.Tensor):
     # over the finite elements: an inf / nan does not set its block's scale,
     # and its code is the e4m3fn NaN with its sign (torch's cast of inf / nan),
-    # as in the MX format and the GPU kernels (``csrc/hsgpu.hip`` fp8_fix_nonfinite)
+    # as in the MX format and the GPU kernels (``csrc/hsquant.hip`` fp8_fix_nonfinite)
     finite = torch.isfinite(blocks)
     amax = torch.where(finite, blocks.abs(), torch.zeros_like(blocks)).amax(dim=1)
     # tensor/tensor division (correctly rounded; a Python-scalar divisor is

@@ -117,12 +117,12 @@ def worker(r, args, q):
         b.launch(0, stream, sync=True)
         checks = {}
         if lib.hsg_rt_memcpy_d2h(back.ptr, u, n) != 0:
-            res["errors"].append(f"iter {k}: d2h U {lib.hsg_rt_last_error()}")
+            res["errors"].append(f"iter {k}: d2h U {lib.hsg_last_error()}")
             break
         checks["U"] = classify(np, np.frombuffer(back.view, dtype=np.uint32, count=n // 4).copy(),
                                want, r, k)
         if lib.hsg_rt_memcpy_d2h(back.ptr, s, n) != 0:
-            res["errors"].append(f"iter {k}: d2h S {lib.hsg_rt_last_error()}")
+            res["errors"].append(f"iter {k}: d2h S {lib.hsg_last_error()}")
             break
         checks["S"] = classify(np, np.frombuffer(back.view, dtype=np.uint32, count=n // 4).copy(),
                                want, r, k)

@@ -30,7 +30,7 @@ def main():
                     t0 = time.perf_counter()
                     p = alloc(0, size, uncached)
                     t1 = time.perf_counter()
-                    assert p, lib.hsg_rt_last_error()
+                    assert p, lib.hsg_last_error()
                     free(p)
                     t2 = time.perf_counter()
                     ta.append((t1 - t0) * 1e3)

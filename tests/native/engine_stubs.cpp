@@ -238,7 +238,7 @@ extern "C" {
 
 int hsg_rt_set_device(int dev) { return dev == 0 ? 0 : -1; }
 
-const char* hsg_rt_last_error() { return "stub"; }
+const char* hsg_last_error() { return "stub"; }  // (hsgpu.hip: the one error channel)
 
 void hsg_rt_trace(const char* what, const void* p, uint64_t n, int kind) {
   (void)what;
@@ -433,7 +433,7 @@ int hsg_sdma_wait(uint64_t handle) {
   return f->rc;
 }
 
-// ---- hashing (hsgpu.hip hs_hash64) ----------------------------------------------------
+// ---- hashing (hshash.hip hs_hash64) ---------------------------------------------------
 
 int hsg_hash64(int dev, int slot, int after_slot, const void* p, uint64_t n, uint64_t first_word,
                int max_grid, int* handle) {
@@ -466,7 +466,7 @@ int hsg_hash64_result(int dev, int slot, int handle, uint64_t* out) {
   return f->rc;
 }
 
-// ---- decode (hsz.hip) and region copies (hsgpu.hip) ------------------------------------
+// ---- decode (hsz.hip) and region copies (hscopy.hip) -----------------------------------
 
 // Stub HSZ1 frames: a 32-byte frame header, then the frame's logical bytes
 // stored as they are (the host engine validates the container, not the

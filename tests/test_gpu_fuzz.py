@@ -1,7 +1,7 @@
 """Randomised GPU checks of the two hand-written data-plane kernels every take
 and restore runs, against PyTorch / the NumPy reference:
 
-* ``hs_copy_nd`` (``csrc/hsgpu.hip``): batches of random strided views --
+* ``hs_copy_nd`` (``csrc/hscopy.hip``): batches of random strided views --
   permuted, step-sliced, narrowed, 1-4-D, same-dtype and casting, into
   contiguous or strided destinations -- each batch ONE launch, every
   destination compared with ``src.to(dst_dtype)`` (bit-exact) and the bytes

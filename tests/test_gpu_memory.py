@@ -142,7 +142,7 @@ def test_vmm_free_gives_the_memory_back(gpu):
     free0, _ = torch.cuda.mem_get_info()
     for i in range(100):
         p = lib.hsg_rt_vmm_alloc(0, 4 * GiB, i % 2)
-        assert p, lib.hsg_rt_last_error()
+        assert p, lib.hsg_last_error()
         assert lib.hsg_rt_vmm_free(p) == 0
     free1, _ = torch.cuda.mem_get_info()
     assert free1 >= free0 - GiB, (free0, free1)

@@ -117,6 +117,12 @@ def test_tables_name_exactly_the_headers_functions():
     assert not HOOKS[1], "shared constants belong in hsgpu_abi.h"
 
 
+def test_hsgpu_has_one_error_getter():
+    # one message channel for the whole library: hsg_last_error
+    exported = set(HSGPU[2]) | set(HOOKS[2])
+    assert [fn for fn in sorted(exported) if fn.endswith("_last_error")] == ["hsg_last_error"]
+
+
 @pytest.mark.parametrize("table,funcs", [(native.HSIO_ABI, HSIO[2]), (native.HSGPU_ABI, HSGPU[2])],
                          ids=["hsio", "hsgpu"])
 def test_every_signature_matches_its_prototype(table, funcs):

@@ -58,7 +58,7 @@ def _mfma_close(got: torch.Tensor, ref: torch.Tensor, x: torch.Tensor, quant: di
     """16-bit Hadamard saves on the GPU rotate on the 16-bit MFMA, which sums
     in its own order: a rotated value can differ from the k-ordered fp32
     reference in its last bit, and an fp8 code next to a rounding boundary
-    then moves by one step (``csrc/hsgpu.hip`` hs_fp8_hadamard_quant16).
+    then moves by one step (``csrc/hsquant.hip`` hs_fp8_hadamard_quant16).
     Bound: NaNs in the same places, every value within 2 block scales, and
     few values off at all."""
     fmax = torch.finfo(got.dtype).max
