@@ -13,7 +13,8 @@ namespace {
 // ---------------------------------------------------------------------------
 // fp8 (OCP e4m3fn) blockwise quantization.  One 64-lane wave owns one block of
 // `block` elements (block = 64 * VPT); amax via 64-wide xor-shuffle reduction,
-// scale = amax / 448, payload via v_cvt_pk_fp8_f32 (gfx950: OCP encoding).
+// scale = max(amax / 448, 2^-126) (fp8_block_scale), payload via
+// v_cvt_pk_fp8_f32 (gfx950: OCP encoding).
 // ---------------------------------------------------------------------------
 
 constexpr float kFp8Max = 448.0f;
@@ -32,6 +33,21 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ float finite_abs(float x) {
   const float a = fabsf(x);
   return a < __builtin_huge_valf() ? a : 0.f;
+}
+
+// Block scale of the f32-scale formats (plain and Hadamard): amax / 448,
+// floored at the smallest normal float (2^-126), 1 for an all-zero block.
+// Without the floor a block with amax below ~1.3e-36 gets a subnormal (or
+// zero) scale whose reciprocal is inf: 0 * inf = NaN, and every non-zero
+// saturates.  With it 1 / scale <= 2^126 is finite, |x| / scale < 448 inside
+// a floored block, zeros stay zeros, and values below 2^-136 flush to zero:
+// that is the format's floor.  Blocks with amax / 448 >= 2^-126 keep the scale
+// and codes they always had.  ops/quant.py _scale_and_quant applies the same
+// rule.
+constexpr float kFp8MinScale = 0x1p-126f;
+
+__device__ __forceinline__ float fp8_block_scale(float amax) {
+  return amax > 0.f ? fmaxf(amax / kFp8Max, kFp8MinScale) : 1.f;
 }
 
 // `word` holds the codes of x[0..3] (byte j <- x[j]); j >= nvalid are left as is
@@ -60,6 +76,7 @@ hs_fp8_quant(const char* __restrict__ src, int32_t src_dtype, int64_t n,
   const int64_t wave0 = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> 6;
   const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
   const int ses = (src_dtype == kF32) ? 4 : 2;
+  const bool out_aligned = (reinterpret_cast<uintptr_t>(out) & 3) == 0;  // 4-B stores below
   for (int64_t b = wave0; b < nblocks; b += nwaves) {
     const int64_t e0 = b * kBlk + int64_t(lane) * VPT;
     float v[VPT];
@@ -75,7 +92,7 @@ hs_fp8_quant(const char* __restrict__ src, int32_t src_dtype, int64_t n,
     // and one multiply per element -- the torch reference (ops/quant.py
     // _scale_and_quant) applies the same rule, so payloads are bit-identical;
     // a division per element made this kernel VALU-bound (profiles/pmc_r2)
-    const float scale = amax > 0.f ? amax / kFp8Max : 1.f;
+    const float scale = fp8_block_scale(amax);
     const float inv = 1.f / scale;
     if (lane == 0) scales[b] = scale;
     uint32_t words[(VPT + 3) / 4];
@@ -90,7 +107,7 @@ hs_fp8_quant(const char* __restrict__ src, int32_t src_dtype, int64_t n,
       words[w] = fp8_fix_nonfinite(static_cast<uint32_t>(word), v + 4 * w,
                                    VPT - 4 * w < 4 ? VPT - 4 * w : 4);
     }
-    if (e0 + VPT <= n && (VPT % 4) == 0) {
+    if (out_aligned && e0 + VPT <= n && (VPT % 4) == 0) {
 #pragma unroll
       for (int w = 0; w < VPT / 4; ++w)
         reinterpret_cast<uint32_t*>(out + e0)[w] = words[w];
@@ -108,10 +125,11 @@ hs_fp8_dequant(const uint8_t* __restrict__ q, const float* __restrict__ scales, 
   constexpr int kBlk = 64 * VPT;
   const int des = (dst_dtype == kF32) ? 4 : (dst_dtype == kF64 ? 8 : 2);
   const int64_t nthreads = int64_t(gridDim.x) * kBlock;
+  const bool q_aligned = (reinterpret_cast<uintptr_t>(q) & 3) == 0;  // 4-B loads below
   for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i * 4 < n; i += nthreads) {
     const int64_t e0 = i * 4;
     uint32_t word;
-    if (e0 + 4 <= n) {
+    if (q_aligned && e0 + 4 <= n) {
       word = reinterpret_cast<const uint32_t*>(q)[i];
     } else {
       word = 0;
@@ -188,9 +206,14 @@ hs_mx8_quant(const char* __restrict__ src, int64_t n, int64_t payload,
   const int64_t wave0 = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> 6;
   const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
   const int64_t nchunks = (n + kChunk - 1) / kChunk;
+  // wave-uniform: the 16-B loads of `src` and the EPL-byte stores of `out`
+  // need their natural alignment (a view with a storage offset has neither);
+  // a misaligned call takes the element path of the tail for every chunk
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(out) & (EPL - 1)) == 0;
   for (int64_t c = wave0; c < nchunks; c += nwaves) {
     const int64_t base = c * kChunk;
-    const bool full = base + kChunk <= n;
+    const bool full = aligned && base + kChunk <= n;
     uint4 raw[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -307,9 +330,13 @@ hs_mx8_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scales
   const int64_t wave0 = (int64_t(blockIdx.x) * kBlock + threadIdx.x) >> 6;
   const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
   const int64_t nchunks = (n + kChunk - 1) / kChunk;
+  // wave-uniform: the EPL-byte loads of `q` and the 16-B stores of `dst` need
+  // their natural alignment; a misaligned call takes the element path
+  const bool aligned = (reinterpret_cast<uintptr_t>(q) & (EPL - 1)) == 0 &&
+                       (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
   for (int64_t c = wave0; c < nchunks; c += nwaves) {
     const int64_t base = c * kChunk;
-    const bool full = base + kChunk <= n;
+    const bool full = aligned && base + kChunk <= n;
     uint32_t raw[U][(EPL + 3) / 4];
     uint8_t sb[U];
 #pragma unroll
@@ -410,7 +437,7 @@ hs_fp8_dequant_v(const uint8_t* __restrict__ q, const float* __restrict__ scales
 // (EPL elements) of a 1 KiB wave segment, U = 4 segments in flight per lane,
 // a block spans LPB = BLK / EPL adjacent lanes (amax: log2(LPB) xor shuffles),
 // and each lane stores its EPL fp8 codes with one vector store.  Same numerics
-// as hs_fp8_quant: scale = amax / 448 (1 if amax == 0), q = cvt(clamp(x * (1 /
+// as hs_fp8_quant: scale = fp8_block_scale(amax), q = cvt(clamp(x * (1 /
 // scale))).  hs_fp8_quant (one block per wave, two 2-B loads per lane) ran at
 // 1.9 TB/s: too little in flight per wave.
 // ---------------------------------------------------------------------------
@@ -466,7 +493,7 @@ hs_fp8_quant_v(const char* __restrict__ src, int64_t n, uint8_t* __restrict__ ou
       for (int j = 0; j < EPL; ++j) amax = fmaxf(amax, finite_abs(v[j]));
 #pragma unroll
       for (int o = 1; o < LPB; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-      const float scale = amax > 0.f ? amax / kFp8Max : 1.f;
+      const float scale = fp8_block_scale(amax);
       const float inv = 1.f / scale;
       const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
       if ((lane % LPB) == 0 && e0 < n) scales[e0 / BLK] = scale;
@@ -594,7 +621,7 @@ hs_fp8_hadamard_quant(const char* __restrict__ src, int64_t n, int64_t n_pad,
       float amax = fmaxf(fmaxf(finite_abs(acc[4 * g4]), finite_abs(acc[4 * g4 + 1])),
                          fmaxf(finite_abs(acc[4 * g4 + 2]), finite_abs(acc[4 * g4 + 3])));
       amax = max_over_32(amax);
-      const float scale = amax > 0.f ? amax / kFp8Max : 1.f;
+      const float scale = fp8_block_scale(amax);
       const float inv = 1.f / scale;
       const int64_t blk = tile * 8 + 2 * g4 + h;
       if (r == 0 && blk < nblocks) scales[blk] = scale;
@@ -674,7 +701,7 @@ __device__ __forceinline__ void hadamard_tile_store(const floatx16& acc, int64_t
     float amax = fmaxf(fmaxf(finite_abs(acc[4 * g4]), finite_abs(acc[4 * g4 + 1])),
                        fmaxf(finite_abs(acc[4 * g4 + 2]), finite_abs(acc[4 * g4 + 3])));
     amax = max_over_32(amax);
-    const float scale = amax > 0.f ? amax / kFp8Max : 1.f;
+    const float scale = fp8_block_scale(amax);
     const float inv = 1.f / scale;
     const int64_t blk = tile * 8 + 2 * g4 + h;
     if (r == 0 && blk < nblocks) scales[blk] = scale;
@@ -809,14 +836,25 @@ hs_fp8_hadamard_dequant8(const uint8_t* __restrict__ q, const float* __restrict_
     b1[j] = (__popc((16 * h + 8 + j) & r) & 1) ? short(0xBF80) : short(0x3F80);
   }
   const bool vec_out = (DES == 2) && (reinterpret_cast<uintptr_t>(dst) & 7) == 0;
+  // wave-uniform: the 16-B loads of `q` need a 16-B aligned payload (e0 is a
+  // multiple of 16); a misaligned one is read byte by byte
+  const bool q_aligned = (reinterpret_cast<uintptr_t>(q) & 15) == 0;
   for (int64_t t0 = wave0 * U; t0 < ntiles; t0 += nwaves * U) {
     mx_u32x4 a[U];
     float sc[U][4];
 #pragma unroll
     for (int u = 0; u < U; ++u) {  // q holds n_pad bytes (a multiple of 32)
       const int64_t e0 = ((t0 + u) * 32 + r) * 32 + 16 * h;
-      a[u] = (e0 + 16 <= n_pad) ? __builtin_nontemporal_load(reinterpret_cast<const mx_u32x4*>(q + e0))
-                                : mx_u32x4{0, 0, 0, 0};
+      if (q_aligned) {
+        a[u] = (e0 + 16 <= n_pad) ? __builtin_nontemporal_load(reinterpret_cast<const mx_u32x4*>(q + e0))
+                                  : mx_u32x4{0, 0, 0, 0};
+      } else {
+        a[u] = mx_u32x4{0, 0, 0, 0};
+        if (e0 + 16 <= n_pad) {
+#pragma unroll
+          for (int j = 0; j < 16; ++j) a[u][j >> 2] |= uint32_t(q[e0 + j]) << (8 * (j & 3));
+        }
+      }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int64_t blk = (t0 + u) * 8 + 2 * g4 + h;

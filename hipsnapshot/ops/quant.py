@@ -35,8 +35,17 @@ rotation ``"none"`` (default): plain blockwise quantization (``hs_fp8_quant`` ke
 one wave per block, 64-lane xor-shuffle amax, ``v_cvt_pk_fp8_f32`` -- gfx950
 converts to OCP e4m3fn natively).
 
-Scale rule (both): ``scale = amax / 448`` (correctly rounded; 1 when the block
-is all zeros), ``q = e4m3fn(clamp(y / scale))`` with round-to-nearest-even.
+Scale rule (both): ``scale = max(amax / 448, 2^-126)`` (the quotient correctly
+rounded; 1 when the block is all zeros), ``q = e4m3fn(clamp(y * (1 / scale)))``
+with round-to-nearest-even.  The floor at the smallest normal float32 keeps
+``1 / scale <= 2^126`` finite: without it a block whose ``amax`` is below about
+1.3e-36 (Adam second moments of rarely touched rows) got a subnormal or zero
+scale, ``1 / scale = inf``, every zero restored as NaN (``0 * inf``) and every
+non-zero as ``+-amax``.  Inside a floored block ``|y| / scale < 448``, zeros
+stay zeros and values below ``2^-136`` flush to zero: that is the format's
+floor.  Blocks with ``amax / 448 >= 2^-126`` are unchanged, and a stored scale
+means what it always did, so older snapshots decode as before.  The kernels
+(``csrc/hsquant.hip`` ``fp8_block_scale``) apply the same rule.
 
 MX layout (default for un-rotated tensors; ``HIPSNAPSHOT_FP8_FORMAT=block``
 selects the fp32-scale layout above)::
@@ -71,6 +80,7 @@ from ..format.serialization import FP8_QUANTIZABLE_DTYPES, dtype_to_string, stri
 from ..io_types import StagedBuffer
 
 FP8_MAX = 448.0
+FP8_MIN_SCALE = 2.0 ** -126  # smallest normal float32: floor of a block's fp32 scale
 DEFAULT_VPT = 2
 GROUP = 32
 
@@ -150,7 +160,11 @@ def _scale_and_quant(blocks: torch.Tensor):
     amax = torch.where(finite, blocks.abs(), torch.zeros_like(blocks)).amax(dim=1)
     # tensor/tensor division (correctly rounded; a Python-scalar divisor is
     # lowered to a reciprocal multiply by torch and differs by 1 ulp)
-    scale = torch.where(amax > 0, amax / torch.full_like(amax, FP8_MAX), torch.ones_like(amax))
+    # floored at the smallest normal float32 (module docstring, "Scale rule")
+    scale = torch.where(amax > 0,
+                        torch.maximum(amax / torch.full_like(amax, FP8_MAX),
+                                      torch.full_like(amax, FP8_MIN_SCALE)),
+                        torch.ones_like(amax))
     # one reciprocal per block, one multiply per element (the kernels' rule)
     inv = torch.ones_like(scale) / scale
     q = torch.where(finite, (blocks * inv[:, None]).clamp(-FP8_MAX, FP8_MAX),
