@@ -347,8 +347,11 @@ void writer_thread(Job* j, bool parked) {
         const ssize_t w = pwrite(b.fd, p + done, len - done, off_t(c.off + done));
         if (w < 0) {
           if (errno == EINTR) continue;
-          if (errno == EINVAL && b.direct) {
-            // the device wants a larger alignment: continue buffered
+          if ((errno == EINVAL || errno == EFAULT) && b.direct) {
+            // EINVAL: the device wants a larger alignment.  EFAULT: the
+            // kernel cannot pin the slot's pages for direct I/O (a
+            // hipHostMalloc slot, where hipHostRegister is unavailable and
+            // the pool has no registered blocks).  Continue buffered.
             const int fl = fcntl(b.fd, F_GETFL);
             if (fl >= 0 && fcntl(b.fd, F_SETFL, fl & ~O_DIRECT) == 0) continue;
           }

@@ -564,6 +564,20 @@ int hsg_is_managed(const void* p) {
   return attr.isManaged ? 1 : 0;
 }
 
+// 1 if `dev` migrates managed pages (hipDeviceAttributeManagedMemory).  Where
+// it does not -- a GPU passed through to a virtual machine without HMM --
+// hipMallocManaged hands out pinned host memory, hipMemAdvise and
+// hipMemPrefetchAsync succeed without effect and hipMemRangeGetAttribute
+// reports nothing: the pages stay in host DRAM.
+int hsg_managed_supported(int dev) {
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeManagedMemory, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return v ? 1 : 0;
+}
+
 void* hsg_managed_alloc(int dev, uint64_t n) {
   hipError_t e = hipSetDevice(dev);
   if (e != hipSuccess) {

@@ -98,6 +98,7 @@ int hsg_mx8_dequantize(int dev, const void* q, const void* scales, int64_t n, vo
 
 // hsgpu.hip: managed memory, stream gate
 int hsg_is_managed(const void* p);
+int hsg_managed_supported(int dev);
 int hsg_managed_location(const void* p, uint64_t n, int* preferred, int* last_prefetch);
 int hsg_managed_place(int dev, const void* p, uint64_t n, int loc, void* stream);
 void* hsg_managed_alloc(int dev, uint64_t n);

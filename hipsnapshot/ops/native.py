@@ -280,6 +280,7 @@ HSGPU_ABI = {
     "hsg_restore_prewarm": (c_int, [c_int, c_uint64, c_uint64, c_uint64, c_int, c_uint64]),
     "hsg_sdma_h2d_submit": (c_int, [c_int, c_void_p, c_void_p, c_uint64, P(c_uint64)]),
     "hsg_is_managed": (c_int, [c_void_p]),
+    "hsg_managed_supported": (c_int, [c_int]),
     "hsg_managed_location": (c_int, [c_void_p, c_uint64, P(c_int), P(c_int)]),
     "hsg_managed_place": (c_int, [c_int, c_void_p, c_uint64, c_int, c_void_p]),
     "hsg_managed_alloc": (c_void_p, [c_int, c_uint64]),
@@ -1103,6 +1104,12 @@ def gate_release(dev: int, value: int) -> None:
 
 def gate_value(dev: int) -> int:
     return int(require_gpu_lib().hsg_gate_value(dev))
+
+
+def managed_supported(dev: int) -> bool:
+    """Whether ``dev`` migrates managed (UVM) pages; where it does not they
+    are pinned host memory and ``managed_place`` has no effect."""
+    return bool(require_gpu_lib().hsg_managed_supported(dev))
 
 
 def managed_location(ptr: int, nbytes: int) -> Tuple[int, int]:
