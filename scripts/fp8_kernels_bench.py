@@ -1,8 +1,14 @@
-"""fp8 quantize / dequantize kernels alone on 1 GiB of bf16 (for rocprofv3
---stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128, MFMA
-Hadamard-32.  Prints one JSON line per kernel with host-timed GB/s of HBM
-traffic (read + written bytes)."""
+"""fp8 quantize / dequantize kernels alone on 512 Mi elements (1 GiB of bf16;
+for rocprofv3 --stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128,
+MFMA Hadamard-32.  Prints one JSON line per kernel with host-timed GB/s of HBM
+traffic (read + written bytes).
 
+    fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [mode ...]
+
+``--offset`` shifts the source and the restored tensor by one element, so
+neither has the alignment of the vector loads and stores."""
+
+import argparse
 import json
 import os
 import sys
@@ -28,23 +34,30 @@ def timeit(fn, iters=10):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
+    ap.add_argument("--offset", action="store_true")
+    ap.add_argument("modes", nargs="*", default=["mx_e8m0", "none", "hadamard32"])
+    args = ap.parse_args()
     dev = 0
     torch.cuda.set_device(dev)
-    modes = sys.argv[1:] or ["mx_e8m0", "none", "hadamard32"]
-    w = torch.empty(512 << 20, dtype=torch.bfloat16, device="cuda:0").normal_()
-    nw = w.numel()
+    modes = args.modes
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    off = 1 if args.offset else 0
+    nw = 512 << 20
+    w = torch.empty(nw + off, dtype=dtype, device="cuda:0").normal_()[off:]
     hs = int(torch.cuda.current_stream().cuda_stream)
     for mode in modes:
         if mode == "mx_e8m0":
             info = quant.fp8_entry_quant_info(w, rotation="none")
         else:
-            os.environ["HIPSNAPSHOT_FP8_SCALE"] = "fp32"
+            os.environ["HIPSNAPSHOT_FP8_FORMAT"] = "block"
             info = quant.fp8_entry_quant_info(w, rotation=mode)
-            del os.environ["HIPSNAPSHOT_FP8_SCALE"]
+            del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         blob = torch.zeros(info["total_bytes"], dtype=torch.uint8, device="cuda:0")
         p = info["payload_bytes"]
         sc = blob[p:] if mode == "mx_e8m0" else blob[p:].view(torch.float32)
-        back = torch.empty_like(w)
+        back = torch.empty(nw + off, dtype=dtype, device="cuda:0")[off:]
         if mode == "mx_e8m0":
             q = lambda: native.mx8_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mx8_dequantize(dev, blob[:nw], sc, back, hs)  # noqa: E731
@@ -54,7 +67,7 @@ def main():
         else:
             q = lambda: native.fp8_hadamard_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.fp8_hadamard_dequantize(dev, blob[:p], sc, back, hs)  # noqa
-        traffic = nw * 2 + info["total_bytes"]
+        traffic = nw * w.element_size() + info["total_bytes"]
         for name, fn in (("quant", q), ("dequant", dq)):
             best, med = timeit(fn)
             print(json.dumps({"kernel": f"{name}_{mode}", "ms_best": round(best * 1e3, 4),
