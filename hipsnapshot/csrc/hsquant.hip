@@ -1,7 +1,9 @@
 // hsquant: K5/K9 quantization kernels of the lossy checkpoint formats --
 // blockwise OCP-fp8 (e4m3fn) with an f32 scale per block, MX fp8 (one E8M0
-// scale byte per 32 elements) and Hadamard-rotated fp8 on the matrix cores --
-// and their hsg_*quantize / hsg_*dequantize entry points.  Wave size is 64.
+// scale byte per 32 elements), Hadamard-rotated fp8 on the matrix cores and
+// MXFP4 (e2m1 nibbles, one E8M0 scale byte per 32 elements, gfx950's scaled
+// fp4 conversions) -- and their hsg_*quantize / hsg_*dequantize entry points.
+// Wave size is 64.
 
 #include <algorithm>
 #include <cstdint>
@@ -368,6 +370,337 @@ __global__ void __launch_bounds__(kBlock)
 hs_fp8_dequant_v(const uint8_t* __restrict__ q, const float* __restrict__ scales, int64_t n,
                  char* __restrict__ dst) {
   stream_dequant<DT, BlockScale<BLK>>(q, scales, n, dst);
+}
+
+// ---------------------------------------------------------------------------
+// MXFP4 (format "fp4_e2m1_mx"): e2m1 codes -- sign in bit 3, bits 0-2 an index
+// into {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- two per byte, element 2i in the low
+// nibble, and one E8M0 scale byte k + 127 per 32 elements.  The rules
+// (ops/quant.py mxfp4_quantize_reference applies the same ones):
+//   * k is the smallest exponent with amax <= 6 * 2^k over the block's finite
+//     elements (frexp: amax = m 2^e, k = e - 3 if m <= 0.75 else e - 2), clamped
+//     to [-127, 127], 0 for a block without a finite non-zero: x * 2^-k is
+//     exact and at most 6, so there is no division and no clamp;
+//   * round to nearest, ties to the even index, the source's sign kept;
+//   * +-inf is code +-6 and does not set the scale;
+//   * e2m1 has no NaN: a block that holds one stores the MX NaN scale 0xFF
+//     and 16 zero payload bytes, and restores as positive quiet NaNs;
+//   * restore is q * 2^k, exact in f32, then the one rounding to the
+//     destination (pack16 / store_from_f32).
+// payload = round_up(ceil(n / 2), 16) bytes, zero from element n on.
+//
+// Quantize (hs_mxfp4_quant): as in the fp8 streams every 16-B load is
+// contiguous across the wave and U = 4 of them are in flight per lane.  A
+// nibble payload has no one-byte-per-element store, so the lanes map
+// differently:
+//   * amax is an unsigned max of |x| bit patterns (monotonic for finite
+//     values; v_pk_max_u16 on the packed 16-bit words), then a 2- or 3-step
+//     xor-shuffle over the 4 (bf16/f16) or 8 (f32) lanes of a block.  A lane
+//     whose max pattern is non-finite -- rare -- goes through its elements once
+//     more, leaves inf out and marks a NaN with the key 0xffffffff, which
+//     survives the max;
+//   * bf16 / f16: the lane's 8 elements go from their packed words straight
+//     through v_cvt_scalef32_pk_fp4_{bf16,f16}, one byte each, into one 4-B
+//     store; the wave's stores are 256 contiguous bytes;
+//   * f32: a 16-B load gives only 2 payload bytes.  Lanes are paired over two
+//     loads u, u + 1: the even lane keeps its half-word of load u and takes
+//     its neighbour's, the odd lane does the same for load u + 1 -- one DPP
+//     quad-perm move per two loads -- so every lane again has one 4-B store
+//     and a store instruction covers 256 contiguous bytes.  (Two adjacent
+//     loads per lane would make each load instruction touch every other 16 B:
+//     the loads, not the stores, carry two thirds of this kernel's traffic.)
+//   * scale bytes: a lane keeps the U bytes of its blocks in one register;
+//     four wave shuffles per chunk collect them so that the chunk's 64 (f32:
+//     32) scale bytes leave as 4-B stores of adjacent lanes.
+// The scaled conversions take the scale as an f32 and read its exponent field
+// only, which is the E8M0 byte itself: k = -127 is the field 0.  On an MI355X
+// they gave the reference's code for every tested input (tests/
+// test_gpu_mxfp4.py): ties go to the even code, a magnitude that rounds to
+// zero keeps its sign, subnormal sources and k = -127 scale exactly, and the
+// first element of a pair lands in the low nibble.  So only what the format
+// defines differently is patched: inf and the NaN block.
+// Dequantize (hs_mxfp4_dequant): a lane reads 4 / 2 / 1 payload bytes and
+// writes 16 B with a nontemporal store, U = 4 steps in flight, the scale per
+// lane.  (With plain stores the f32 restore of 2 GiB took 0.544 ms beside MX
+// fp8's 0.529 ms; nontemporal ones brought it to 0.535 ms and the bf16 restore
+// from 0.272 to 0.263 ms -- docs/architecture.md section 4.)
+// v_cvt_scalef32_pk_f32_fp4 decodes the nibbles with scale 1; 2^k is applied
+// by v_ldexp_f32 as in MX fp8, which is exact down to subnormals and gives inf
+// on overflow (a finite |x| >= 0.875 * 2^128 rounds to a code whose product
+// overflows f32: the format's known edge, as in MX fp8).  The scaled forms
+// v_cvt_scalef32_pk_{bf16,f16}_fp4 are not used: what they do with subnormal
+// or overflowing 16-bit results is not documented, and the restore rule is
+// stated on the f32 product.
+// A source, payload, scale array or destination without the vector alignment
+// (wave-uniform test) and the tail chunk take the element path.
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kFp4NanKey = 0xffffffffu;
+constexpr uint32_t kE8m0Nan = 0xffu;
+
+typedef unsigned short mx_u16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 mx_bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 mx_f16x2 __attribute__((ext_vector_type(2)));
+typedef float mx_f32x2 __attribute__((ext_vector_type(2)));
+
+template <int DT>
+constexpr uint32_t kInfBits = DT == kF32 ? 0x7f800000u : (DT == kBF16 ? 0x7f80u : 0x7c00u);
+
+// |x| bits and sign of element j of a 16-B piece
+template <int DT>
+__device__ __forceinline__ uint32_t fp4_abs_bits(const mx_u32x4& w, int j) {
+  if constexpr (DT == kF32) return w[j] & 0x7fffffffu;
+  else return (w[j >> 1] >> (16 * (j & 1))) & 0x7fffu;
+}
+
+template <int DT>
+__device__ __forceinline__ uint32_t fp4_sign(const mx_u32x4& w, int j) {
+  if constexpr (DT == kF32) return w[j] >> 31;
+  else return (w[j >> 1] >> (16 * (j & 1) + 15)) & 1u;
+}
+
+// largest finite |x| pattern of a lane's 16 B, kFp4NanKey if one is a NaN;
+// `nonfinite`: the piece holds an inf or a NaN
+template <int DT>
+__device__ __forceinline__ uint32_t fp4_lane_key(const mx_u32x4& w, bool& nonfinite) {
+  constexpr uint32_t kInf = kInfBits<DT>;
+  uint32_t a;
+  if constexpr (DT == kF32) {
+    a = max(max(w[0] & 0x7fffffffu, w[1] & 0x7fffffffu),
+            max(w[2] & 0x7fffffffu, w[3] & 0x7fffffffu));
+  } else {
+    mx_u16x2 m = __builtin_bit_cast(mx_u16x2, w[0] & 0x7fff7fffu);
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+      m = __builtin_elementwise_max(m, __builtin_bit_cast(mx_u16x2, w[i] & 0x7fff7fffu));
+    a = max(uint32_t(m[0]), uint32_t(m[1]));
+  }
+  nonfinite = a >= kInf;
+  if (nonfinite) {
+    a = 0;
+#pragma unroll
+    for (int j = 0; j < (DT == kF32 ? 4 : 8); ++j) {
+      const uint32_t p = fp4_abs_bits<DT>(w, j);
+      a = p > kInf ? kFp4NanKey : (p < kInf ? max(a, p) : a);
+    }
+  }
+  return a;
+}
+
+// E8M0 byte of a block from its amax key (finite pattern or kFp4NanKey)
+template <int DT>
+__device__ __forceinline__ uint32_t mxfp4_scale_byte(uint32_t key) {
+  if (key == kFp4NanKey) return kE8m0Nan;
+  float amax;
+  if constexpr (DT == kF32) amax = __uint_as_float(key);
+  else amax = mx_unpack<DT>(key, 0);
+  int k = 0;
+  if (amax > 0.f) {
+    int e;
+    const float m = frexpf(amax, &e);
+    k = (m <= 0.75f) ? e - 3 : e - 2;
+    k = k < -127 ? -127 : (k > 127 ? 127 : k);
+  }
+  return static_cast<uint32_t>(k + 127);
+}
+
+// codes of a lane's 16 B under scale byte `sb`: 8 nibbles (bf16 / f16) or 4
+// (f32, low half-word), element j in nibble j.  The conversions divide by
+// 2^(exponent field of `scale`) and round to nearest even.  Patched after
+// them: the code of an inf (sign | 7, whatever the conversion saturates to)
+// and the all-zero payload of a NaN block.
+template <int DT>
+__device__ __forceinline__ uint32_t fp4_pack(const mx_u32x4& w, uint32_t sb, bool nonfinite) {
+  if (sb == kE8m0Nan) return 0;
+  const float scale = __uint_as_float(sb << 23);
+  // (the words as scalars first: __builtin_bit_cast of a vector element
+  // `w[i]` reads element 0 whatever i is)
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+  uint32_t r = 0;
+  if constexpr (DT == kF32) {
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, __uint_as_float(w0), __uint_as_float(w1), scale, 0);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, __uint_as_float(w2), __uint_as_float(w3), scale, 1);
+  } else if constexpr (DT == kBF16) {
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(r, __builtin_bit_cast(mx_bf16x2, w0), scale, 0);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(r, __builtin_bit_cast(mx_bf16x2, w1), scale, 1);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(r, __builtin_bit_cast(mx_bf16x2, w2), scale, 2);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(r, __builtin_bit_cast(mx_bf16x2, w3), scale, 3);
+  } else {
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(r, __builtin_bit_cast(mx_f16x2, w0), scale, 0);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(r, __builtin_bit_cast(mx_f16x2, w1), scale, 1);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(r, __builtin_bit_cast(mx_f16x2, w2), scale, 2);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f16(r, __builtin_bit_cast(mx_f16x2, w3), scale, 3);
+  }
+  if (nonfinite) {
+#pragma unroll
+    for (int j = 0; j < (DT == kF32 ? 4 : 8); ++j)
+      if (fp4_abs_bits<DT>(w, j) == kInfBits<DT>)
+        r = (r & ~(0xfu << (4 * j))) | ((7u | (fp4_sign<DT>(w, j) << 3)) << (4 * j));
+  }
+  return r;
+}
+
+// `out` holds `payload` >= ceil(n / 2) bytes, `scales` ceil(n / 32)
+template <int DT>
+__global__ void __launch_bounds__(kBlock)
+hs_mxfp4_quant(const char* __restrict__ src, int64_t n, int64_t payload,
+               uint8_t* __restrict__ out, uint8_t* __restrict__ scales) {
+  constexpr int ES = (DT == kF32) ? 4 : 2;
+  constexpr int EPL = 16 / ES;   // elements per lane per load
+  constexpr int LPB = 32 / EPL;  // lanes per block
+  constexpr int BPL = 64 / LPB;  // blocks (scale bytes) per wave load
+  constexpr int U = kStreamU;
+  static_assert(U == 4, "a lane packs its U scale bytes into one word");
+  constexpr int64_t kChunk = 64LL * EPL * U;
+  const int lane = threadIdx.x & 63;
+  // the wave index through readfirstlane: `base` and `full` are then scalars and
+  // the choice between the vector and the element path is a scalar branch
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(out) & 3) == 0 &&
+                       (reinterpret_cast<uintptr_t>(scales) & 3) == 0;
+  for (int64_t base = wave0 * kChunk; base < n; base += nwaves * kChunk) {
+    const bool full = aligned && base + kChunk <= n;
+    mx_u32x4 raw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      raw[u] = full ? __builtin_nontemporal_load(reinterpret_cast<const mx_u32x4*>(src + e0 * ES))
+                    : load16_elems<ES>(src, e0, n);
+    }
+    uint32_t code[U];
+    uint32_t sbytes = 0;  // byte u: the scale of this lane's block of load u
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bool nonfinite;
+      uint32_t key = fp4_lane_key<DT>(raw[u], nonfinite);
+#pragma unroll
+      for (int o = 1; o < LPB; o <<= 1) key = max(key, uint32_t(__shfl_xor(int(key), o, 64)));
+      const uint32_t sb = mxfp4_scale_byte<DT>(key);
+      sbytes |= sb << (8 * u);
+      code[u] = fp4_pack<DT>(raw[u], sb, nonfinite);
+    }
+    if (full) {
+      if constexpr (EPL == 8) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+          __builtin_nontemporal_store(code[u], reinterpret_cast<uint32_t*>(out + (e0 >> 1)));
+        }
+      } else {
+        const bool odd = lane & 1;
+#pragma unroll
+        for (int u = 0; u < U; u += 2) {
+          // even lane: (own, lane + 1) half-words of load u; odd lane:
+          // (lane - 1, own) of load u + 1
+          const uint32_t other = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(
+              static_cast<int>(odd ? code[u] : code[u + 1]), 0xB1, 0xF, 0xF, false));  // lane ^ 1
+          const uint32_t word = odd ? ((other & 0xffffu) | (code[u + 1] << 16))
+                                    : ((code[u] & 0xffffu) | (other << 16));
+          const int64_t e0 = base + (int64_t(u + odd) * 64 + (lane & ~1)) * EPL;
+          __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(out + (e0 >> 1)));
+        }
+      }
+      // scale byte s of the chunk is byte s / BPL of `sbytes` in lane
+      // (s % BPL) * LPB; lane l < U * BPL / 4 stores bytes 4 l .. 4 l + 3
+      const int s = (4 * lane) % (U * BPL);
+      const int l0 = (s % BPL) * LPB;
+      uint32_t word = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        word |= ((uint32_t(__shfl(int(sbytes), l0 + j * LPB, 64)) >> (8 * (s / BPL))) & 0xffu)
+                << (8 * j);
+      if (lane < U * BPL / 4)
+        __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(scales + base / 32) + lane);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+        if ((lane % LPB) == 0 && e0 < n) scales[e0 / 32] = static_cast<uint8_t>(sbytes >> (8 * u));
+        for (int b = 0; b < EPL / 2; ++b) {
+          const int64_t at = (e0 >> 1) + b;
+          if (at < payload) out[at] = 2 * at < n ? static_cast<uint8_t>(code[u] >> (8 * b)) : 0;
+        }
+      }
+    }
+  }
+}
+
+// 16 B of restored output (8 x bf16/f16, 4 x f32 or 2 x f64), written once
+// and not read again by this kernel: a nontemporal store
+template <int DT>
+__device__ __forceinline__ void fp4_store16(char* p, const float* f) {
+  mx_u32x4 w;
+  if constexpr (DT == kF32) {
+    w = mx_u32x4{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
+                 __float_as_uint(f[3])};
+  } else if constexpr (DT == kF64) {
+    const uint64_t a = __builtin_bit_cast(uint64_t, static_cast<double>(f[0]));
+    const uint64_t b = __builtin_bit_cast(uint64_t, static_cast<double>(f[1]));
+    w = mx_u32x4{uint32_t(a), uint32_t(a >> 32), uint32_t(b), uint32_t(b >> 32)};
+  } else {
+    w = mx_u32x4{pack16<DT>(f[0], f[1]), pack16<DT>(f[2], f[3]), pack16<DT>(f[4], f[5]),
+                 pack16<DT>(f[6], f[7])};
+  }
+  __builtin_nontemporal_store(w, reinterpret_cast<mx_u32x4*>(p));
+}
+
+template <int DT>
+__global__ void __launch_bounds__(kBlock)
+hs_mxfp4_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scales, int64_t n,
+                 char* __restrict__ dst) {
+  constexpr int DES = (DT == kF32) ? 4 : (DT == kF64 ? 8 : 2);
+  constexpr int EPL = 16 / DES;  // elements per lane per step = one 16-B store
+  constexpr int QB = EPL / 2;    // payload bytes per lane per step
+  constexpr int U = kStreamU;
+  constexpr int64_t kChunk = 64LL * EPL * U;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(q) & (QB - 1)) == 0 &&
+                       (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  for (int64_t base = wave0 * kChunk; base < n; base += nwaves * kChunk) {
+    const bool full = aligned && base + kChunk <= n;
+    uint32_t raw[U];
+    uint32_t sc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      if (full) {
+        if constexpr (QB == 4) raw[u] = *reinterpret_cast<const uint32_t*>(q + (e0 >> 1));
+        else if constexpr (QB == 2) raw[u] = *reinterpret_cast<const uint16_t*>(q + (e0 >> 1));
+        else raw[u] = q[e0 >> 1];
+      } else {
+        raw[u] = 0;
+        for (int b = 0; b < QB && e0 + 2 * b < n; ++b) raw[u] |= uint32_t(q[(e0 >> 1) + b]) << (8 * b);
+      }
+      sc[u] = e0 < n ? scales[e0 / 32] : 0u;  // past n: nothing stored
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      mx_f32x2 p[4];  // the byte select must be an immediate
+      p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 0);
+      if constexpr (QB >= 2) p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 1);
+      if constexpr (QB == 4) {
+        p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 2);
+        p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 3);
+      }
+      const int k = int(sc[u]) - 127;
+      float f[EPL];
+#pragma unroll
+      for (int j = 0; j < EPL; ++j)
+        f[j] = sc[u] == kE8m0Nan ? __builtin_nanf("") : ldexpf(p[j >> 1][j & 1], k);
+      if (full) {
+        fp4_store16<DT>(dst + e0 * DES, f);
+      } else {
+        for (int j = 0; j < EPL && e0 + j < n; ++j) store_from_f32(dst + (e0 + j) * DES, DT, f[j]);
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -901,6 +1234,32 @@ int hsg_mx8_dequantize(int dev, const void* q, const void* scales, int64_t n, vo
     return launch(hs_mx8_dequant<decltype(dt)::value>, grid, stream, q, scales, n, dst);
   });
   return rc == kNoKernel ? unsupported_dtype("mx8 dest", dst_dtype) : rc;
+}
+
+// MXFP4: src (bf16/f16/f32, contiguous, n elements) -> out [payload =
+// round_up(ceil(n / 2), 16) bytes of e2m1 nibbles, zero from element n on] +
+// scales [ceil(n / 32) E8M0 bytes].  Every output byte is written.
+int hsg_mxfp4_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out,
+                       void* scales, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  const int64_t payload = ((n + 1) / 2 + 15) / 16 * 16;
+  const int grid = grid_for(n, stream_chunk(src_dtype), 256 * 16);
+  const int rc = for_dtype<false>(src_dtype, [&](auto dt) {
+    return launch(hs_mxfp4_quant<decltype(dt)::value>, grid, stream, src, n, payload, out, scales);
+  });
+  return rc == kNoKernel ? unsupported_dtype("mxfp4 source", src_dtype) : rc;
+}
+
+int hsg_mxfp4_dequantize(int dev, const void* q, const void* scales, int64_t n, void* dst,
+                         int dst_dtype, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  const int grid = grid_for(n, stream_chunk(dst_dtype), 256 * 16);
+  const int rc = for_dtype<true>(dst_dtype, [&](auto dt) {
+    return launch(hs_mxfp4_dequant<decltype(dt)::value>, grid, stream, q, scales, n, dst);
+  });
+  return rc == kNoKernel ? unsupported_dtype("mxfp4 dest", dst_dtype) : rc;
 }
 
 // Hadamard-rotated fp8: payload `out` has n_pad = round_up(n, 32) bytes,

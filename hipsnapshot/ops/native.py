@@ -260,6 +260,9 @@ HSGPU_ABI = {
                                             c_void_p]),
     "hsg_mx8_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "hsg_mx8_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "hsg_mxfp4_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "hsg_mxfp4_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                     c_void_p]),
     "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
                                    c_int, c_int, c_int, c_int, P(c_int)]),
     "hsg_drain_wait": (c_int, [c_void_p, P(c_uint64), P(c_uint64), c_char_p, P(c_double)]),
@@ -850,6 +853,41 @@ def mx8_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch.T
     assert q.numel() >= n and scales.numel() >= (n + 31) // 32
     _check(lib.hsg_mx8_dequantize(dev, q.data_ptr(), scales.data_ptr(), n, dst.data_ptr(),
                                   dtype_code(dst.dtype), stream_handle), "hsg_mx8_dequantize")
+
+
+def mxfp4_payload_bytes(n: int) -> int:
+    return ((n + 1) // 2 + 15) // 16 * 16
+
+
+def mxfp4_chunk_elems(dtype: torch.dtype) -> int:
+    """Elements one wave of hs_mxfp4_quant / hs_mxfp4_dequant takes per step:
+    64 lanes x 16 B x 4 in flight (csrc/hsquant.hip kStreamU)."""
+    return 64 * 4 * (16 // torch.empty(0, dtype=dtype).element_size())
+
+
+def mxfp4_quantize(dev: int, src: torch.Tensor, out: torch.Tensor, scales: torch.Tensor,
+                   stream_handle: int) -> None:
+    """MXFP4 (e2m1 nibbles + E8M0 scale per 32 elements, hs_mxfp4_quant):
+    ``out`` gets round_up(ceil(n / 2), 16) bytes (element 2i in the low nibble
+    of byte i, zero from element n on), ``scales`` ceil(n / 32)."""
+    lib = require_gpu_lib()
+    n = src.numel()
+    assert src.is_contiguous() and dtype_code(src.dtype) in (10, 11, 12)
+    assert out.numel() >= mxfp4_payload_bytes(n) and scales.numel() >= (n + 31) // 32
+    assert out.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _check(lib.hsg_mxfp4_quantize(dev, src.data_ptr(), dtype_code(src.dtype), n, out.data_ptr(),
+                                  scales.data_ptr(), stream_handle), "hsg_mxfp4_quantize")
+
+
+def mxfp4_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch.Tensor,
+                     stream_handle: int) -> None:
+    lib = require_gpu_lib()
+    n = dst.numel()
+    assert dst.is_contiguous() and dtype_code(dst.dtype) in (10, 11, 12, 13)
+    assert q.numel() >= (n + 1) // 2 and scales.numel() >= (n + 31) // 32
+    assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _check(lib.hsg_mxfp4_dequantize(dev, q.data_ptr(), scales.data_ptr(), n, dst.data_ptr(),
+                                    dtype_code(dst.dtype), stream_handle), "hsg_mxfp4_dequantize")
 
 
 # hsg_drain_start `flags` and the buffers hsg_drain_wait / hsg_restore_wait

@@ -1,9 +1,15 @@
 """fp8 quantize / dequantize kernels alone on 512 Mi elements (1 GiB of bf16;
 for rocprofv3 --stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128,
-MFMA Hadamard-32.  Prints one JSON line per kernel with host-timed GB/s of HBM
-traffic (read + written bytes).
+MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32).  Prints one JSON line per
+kernel with host-timed GB/s of HBM traffic (read + written bytes), the time
+between device events around the call, and GB/s of the tensor alone (source
+bytes of a quantize, destination bytes of a dequantize).
 
-    fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [mode ...]
+    fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [mode ...]
+
+Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``.  ``--rounds R`` goes
+through the list of modes R times, so that two modes alternate and the spread
+of one mode's repeats is seen beside the difference between the two.
 
 ``--offset`` shifts the source and the restored tensor by one element, so
 neither has the alignment of the vector loads and stores."""
@@ -22,26 +28,32 @@ from hipsnapshot.ops import native, quant  # noqa: E402
 
 
 def timeit(fn, iters=10):
+    """(host best, host median, event best, event median) seconds."""
     fn()
     torch.cuda.synchronize()
-    ts = []
+    ts, es = [], []
     for _ in range(iters):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
+        start.record()
         fn()
+        end.record()
         torch.cuda.synchronize()
         ts.append(time.perf_counter() - t0)
-    return min(ts), sorted(ts)[len(ts) // 2]
+        es.append(start.elapsed_time(end) * 1e-3)
+    return min(ts), sorted(ts)[len(ts) // 2], min(es), sorted(es)[len(es) // 2]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
     ap.add_argument("--offset", action="store_true")
+    ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("modes", nargs="*", default=["mx_e8m0", "none", "hadamard32"])
     args = ap.parse_args()
     dev = 0
     torch.cuda.set_device(dev)
-    modes = args.modes
+    modes = args.modes * args.rounds
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     off = 1 if args.offset else 0
     nw = 512 << 20
@@ -50,17 +62,24 @@ def main():
     for mode in modes:
         if mode == "mx_e8m0":
             info = quant.fp8_entry_quant_info(w, rotation="none")
+        elif mode == "mxfp4":
+            os.environ["HIPSNAPSHOT_FP8_FORMAT"] = "mxfp4"
+            info = quant.fp8_entry_quant_info(w, rotation="none")
+            del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         else:
             os.environ["HIPSNAPSHOT_FP8_FORMAT"] = "block"
             info = quant.fp8_entry_quant_info(w, rotation=mode)
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         blob = torch.zeros(info["total_bytes"], dtype=torch.uint8, device="cuda:0")
         p = info["payload_bytes"]
-        sc = blob[p:] if mode == "mx_e8m0" else blob[p:].view(torch.float32)
+        sc = blob[p:] if mode in ("mx_e8m0", "mxfp4") else blob[p:].view(torch.float32)
         back = torch.empty(nw + off, dtype=dtype, device="cuda:0")[off:]
         if mode == "mx_e8m0":
             q = lambda: native.mx8_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mx8_dequantize(dev, blob[:nw], sc, back, hs)  # noqa: E731
+        elif mode == "mxfp4":
+            q = lambda: native.mxfp4_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
+            dq = lambda: native.mxfp4_dequantize(dev, blob[:p], sc, back, hs)  # noqa: E731
         elif mode == "none":
             q = lambda: native.fp8_quantize(dev, w, blob[:p], sc, info["vpt"], hs)  # noqa: E731
             dq = lambda: native.fp8_dequantize(dev, blob[:nw], sc, back, info["vpt"], hs)  # noqa
@@ -69,11 +88,16 @@ def main():
             dq = lambda: native.fp8_hadamard_dequantize(dev, blob[:p], sc, back, hs)  # noqa
         traffic = nw * w.element_size() + info["total_bytes"]
         for name, fn in (("quant", q), ("dequant", dq)):
-            best, med = timeit(fn)
+            best, med, ev_best, ev_med = timeit(fn)
+            tensor = nw * w.element_size()
             print(json.dumps({"kernel": f"{name}_{mode}", "ms_best": round(best * 1e3, 4),
                               "TBps_best": round(traffic / best / 1e12, 3),
                               "TBps_median": round(traffic / med / 1e12, 3),
-                              "traffic_bytes": traffic}), flush=True)
+                              "traffic_bytes": traffic,
+                              "event_ms_best": round(ev_best * 1e3, 4),
+                              "event_ms_median": round(ev_med * 1e3, 4),
+                              "tensor_GBps_event_median": round(tensor / ev_med / 1e9, 1)}),
+                  flush=True)
         del blob, back
 
 
