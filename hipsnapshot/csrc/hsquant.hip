@@ -1008,6 +1008,31 @@ __device__ __forceinline__ hs_i16x8 fp8x8_to_bf16x8(uint32_t w0, uint32_t w1) {
   return o;
 }
 
+// The 4x4 transpose of 16-bit elements over a quad of lanes and its store.
+// In: lane r holds rows 0..3 of column r as (A.lo, A.hi, B.lo, B.hi); `rows`
+// points at row 0, rows are 64 B apart.  Out: lane r writes row r & 3, columns
+// (r & ~3) .. +3, as one 8-B store.
+__device__ __forceinline__ void hada_store_quad16(uint32_t A, uint32_t B, int r, char* rows) {
+  // stage 1 (lanes ^ 1): 2x2 transposes of 16-bit elements
+  const uint32_t A1 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(A), 0xB1, 0xF, 0xF, false));
+  const uint32_t B1 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(B), 0xB1, 0xF, 0xF, false));
+  if (r & 1) {
+    A = __builtin_amdgcn_perm(A, A1, 0x07060302u);  // (partner.hi, mine.hi)
+    B = __builtin_amdgcn_perm(B, B1, 0x07060302u);
+  } else {
+    A = __builtin_amdgcn_perm(A1, A, 0x05040100u);  // (mine.lo, partner.lo)
+    B = __builtin_amdgcn_perm(B1, B, 0x05040100u);
+  }
+  // stage 2 (lanes ^ 2): swap 32-bit words
+  const uint32_t X = (r & 2) ? A : B;
+  const uint32_t R = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(X), 0x4E, 0xF, 0xF, false));
+  if (r & 2) A = R; else B = R;
+  mx_u32x2 w;
+  w.x = A;
+  w.y = B;
+  __builtin_nontemporal_store(w, reinterpret_cast<mx_u32x2*>(rows + ((r & 3) * 32 + (r & ~3)) * 2));
+}
+
 template <int DT, int U>
 __global__ void __launch_bounds__(kBlock)
 hs_fp8_hadamard_dequant8(const uint8_t* __restrict__ q, const float* __restrict__ scales,
@@ -1058,27 +1083,9 @@ hs_fp8_hadamard_dequant8(const uint8_t* __restrict__ q, const float* __restrict_
           for (int g4 = 0; g4 < 4; ++g4) {
             const float s = sc[u][g4] * (1.f / 32.f);
             // lane slot i = row 8 g4 + 4 h + i, column r (two 16-bit rows per word)
-            uint32_t A = pack16<DT>(acc[4 * g4] * s, acc[4 * g4 + 1] * s);
-            uint32_t B = pack16<DT>(acc[4 * g4 + 2] * s, acc[4 * g4 + 3] * s);
-            // stage 1 (lanes ^ 1): 2x2 transposes of 16-bit elements
-            const uint32_t A1 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(A), 0xB1, 0xF, 0xF, false));
-            const uint32_t B1 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(B), 0xB1, 0xF, 0xF, false));
-            if (r & 1) {
-              A = __builtin_amdgcn_perm(A, A1, 0x07060302u);  // (partner.hi, mine.hi)
-              B = __builtin_amdgcn_perm(B, B1, 0x07060302u);
-            } else {
-              A = __builtin_amdgcn_perm(A1, A, 0x05040100u);  // (mine.lo, partner.lo)
-              B = __builtin_amdgcn_perm(B1, B, 0x05040100u);
-            }
-            // stage 2 (lanes ^ 2): swap 32-bit words
-            const uint32_t X = (r & 2) ? A : B;
-            const uint32_t R = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(X), 0x4E, 0xF, 0xF, false));
-            if (r & 2) A = R; else B = R;
-            const int64_t row = tile * 32 + 8 * g4 + 4 * h + (r & 3);
-            mx_u32x2 w;
-            w.x = A;
-            w.y = B;
-            __builtin_nontemporal_store(w, reinterpret_cast<mx_u32x2*>(dst + (row * 32 + (r & ~3)) * 2));
+            hada_store_quad16(pack16<DT>(acc[4 * g4] * s, acc[4 * g4 + 1] * s),
+                              pack16<DT>(acc[4 * g4 + 2] * s, acc[4 * g4 + 3] * s), r,
+                              dst + (tile * 32 + 8 * g4 + 4 * h) * 64);
           }
         }
       } else {
@@ -1087,6 +1094,260 @@ hs_fp8_hadamard_dequant8(const uint8_t* __restrict__ q, const float* __restrict_
           const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
           const int64_t e = (tile * 32 + row) * 32 + r;
           if (e < n) store_from_f32(dst + e * DES, DT, acc[i] * (sc[u][i >> 2] * (1.f / 32.f)));
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Hadamard-rotated MXFP4 (format "fp4_e2m1_mx", rotation "hadamard32"): every
+// group of 32 is rotated by H and the 32 rotated values are ONE MX block --
+// one E8M0 byte and 16 bytes of e2m1 nibbles per group, under the MXFP4 rules
+// above except that a group with any non-finite rotated value (an inf, a NaN
+// or an overflowed sum) stores 0xFF and zeros and restores as quiet NaNs.
+// blob = n_pad / 2 payload bytes + n_pad / 32 scale bytes, n_pad =
+// round_up(n, 32); ops/quant.py states the rules.
+//
+// One wave owns a tile of 32 groups, as the fp8 Hadamard kernels do, but the
+// operands are swapped: H is symmetric, so D = H * X^T puts Y[group j]
+// [element i] at D[i][j], and with the C/D map (register i of lane (r, h) =
+// row (i&3) + 8(i>>2) + 4h, column r) lane (r, h) holds, for group r, the 16
+// rotated elements 8g + 4h + 0..3 (g = 0..3) in its own registers.  The group
+// is the scale block, so nothing of the epilogue crosses more than the two
+// lanes r and r + 32 (v_permlane32_swap: no LDS), where the fp8 epilogue does
+// four 32-lane reductions per tile:
+//   * loads as in the fp8 kernels, now the B operand: f32 lane (r, h) reads
+//     X[r][16h .. 16h+15] and runs 16 x v_mfma_f32_32x32x2_f32 with A =
+//     H[r][16h + t] -- the products and the k order of HADAMARD_K_ORDER, so an
+//     f32 source reproduces the reference byte for byte; bf16 / f16 read the
+//     fragments X[r][16s + 8h ..+7] for 2 x v_mfma_f32_32x32x16, which sums in
+//     the hardware's order (a code on a rounding boundary can move, as for
+//     hadamard32);
+//   * amax: unsigned max over the lane's 16 |y| patterns, one swap with the
+//     other half; a pattern >= inf makes the group a NaN group;
+//   * codes: v_cvt_scalef32_pk_fp4_f32 on register pairs.  Quad g becomes
+//     half-word 2g + h of the group's 16 bytes; one swap of the two packed
+//     words and two v_perm leave lane (r, h) with bytes 8h .. 8h+7: an 8-B
+//     store per lane, 512 contiguous bytes per store instruction;
+//   * scale bytes: OR-ed over each quad of lanes (two DPP moves), 4-B stores.
+// Dequantize: lane (r, h) reads the 8 payload bytes of codes 16h .. 16h+15 of
+// group r (512 contiguous bytes per tile) and decodes them to bf16 (exact) for
+// 2 x v_mfma_f32_32x32x16_bf16 against H[16h + 8s + j][r].  A sum of 32 e2m1
+// values is a multiple of 0.5 of magnitude <= 192: exact in any order, so
+// restores are bit-identical to the torch reference; v_ldexp_f32 by k - 5 is
+// the only other step.  The codes are the A operand here, NOT the transposed
+// form of the quantizer.  Transposed, a lane owns 16 consecutive elements of
+// one group after eight half-wave swaps, one scale byte per lane, but a store
+// instruction then writes 16-B pieces 32 B (bf16) or 64 B (f32) apart: the
+// restore of 512 Mi elements took 0.63 ms (bf16) and 1.91 ms (f32) beside
+// hadamard32's 0.44 and 0.58 ms (profiles/mxfp4_hadamard/first_design_*).
+// With the codes as A, register i is group (i&3) + 8(i>>2) + 4h, element r,
+// as in hs_fp8_hadamard_dequant8: every store instruction writes whole groups
+// (16-bit: through that kernel's lane-quad transpose, 8 B per lane), and a
+// lane reads its 16 scale bytes as four words.  bf16: 0.28 ms, f32: 0.80 ms.
+// The last tiles, and a source / payload / scale array / destination without
+// the vector alignment (wave-uniform test), load and store element by element.
+// ---------------------------------------------------------------------------
+
+// tiles per iteration: 4 (bf16 / f16) or 8 (f32) 16-B loads in flight per lane
+// (one f32 tile per iteration: 0.58 - 0.66 ms for 2 GiB, two: 0.57 - 0.64 ms)
+constexpr int kFp4hQuantU = 2;
+constexpr int kFp4hDequantU = 2;
+
+// v_permlane32_swap: `a` of lanes 32..63 <-> `b` of lanes 0..31
+__device__ __forceinline__ void half_swap(uint32_t& a, uint32_t& b) {
+  const auto s = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+  a = s[0];
+  b = s[1];
+}
+
+// Scale byte and payload bytes 8h .. 8h+7 (`lo`, `hi`) of group r from the
+// rotated tile.  Called by the whole wave.
+__device__ __forceinline__ void fp4h_encode(const floatx16& acc, uint32_t& sb, uint32_t& lo,
+                                            uint32_t& hi) {
+  uint32_t key = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) key = max(key, __float_as_uint(acc[i]) & 0x7fffffffu);
+  uint32_t other = key;
+  half_swap(key, other);  // one of the two is the partner's, the other this lane's
+  key = max(key, other);
+  const bool nan = key >= kInfBits<kF32>;
+  sb = nan ? kE8m0Nan : mxfp4_scale_byte<kF32>(key);
+  const float scale = __uint_as_float(sb << 23);
+  // w0: quads 0, 1 = half-words (h, 2 + h); w1: quads 2, 3 = (4 + h, 6 + h)
+  uint32_t w0 = 0, w1 = 0;
+  w0 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w0, acc[0], acc[1], scale, 0);
+  w0 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w0, acc[2], acc[3], scale, 1);
+  w0 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w0, acc[4], acc[5], scale, 2);
+  w0 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w0, acc[6], acc[7], scale, 3);
+  w1 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w1, acc[8], acc[9], scale, 0);
+  w1 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w1, acc[10], acc[11], scale, 1);
+  w1 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w1, acc[12], acc[13], scale, 2);
+  w1 = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w1, acc[14], acc[15], scale, 3);
+  if (nan) w0 = w1 = 0;
+  // h = 0 gives (4, 6) and takes (1, 3); h = 1 gives (1, 3) and takes (4, 6):
+  // both then hold (even, even + 2) in w0 and (odd, odd + 2) in w1
+  half_swap(w0, w1);
+  lo = __builtin_amdgcn_perm(w1, w0, 0x05040100u);  // (w0.lo, w1.lo)
+  hi = __builtin_amdgcn_perm(w1, w0, 0x07060302u);  // (w0.hi, w1.hi)
+}
+
+// `out` holds 16 * nblocks bytes, `scales` nblocks, nblocks = ceil(n / 32)
+template <int DT, int U>
+__global__ void __launch_bounds__(kBlock)
+hs_mxfp4_hadamard_quant(const char* __restrict__ src, int64_t n, int64_t nblocks,
+                        uint8_t* __restrict__ out, uint8_t* __restrict__ scales) {
+  constexpr int ES = (DT == kF32) ? 4 : 2;
+  constexpr int NV = ES;  // 16-B pieces of a lane's 16 elements
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t ntiles = (nblocks + 31) / 32;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(out) & 7) == 0 &&
+                       (reinterpret_cast<uintptr_t>(scales) & 3) == 0;
+  for (int64_t t0 = wave0 * U; t0 < ntiles; t0 += nwaves * U) {
+    const bool full = aligned && (t0 + U) * 1024 <= n;
+    mx_u32x4 x[U][NV];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        // f32: X[r][16h + 4v ..+3]; 16-bit: X[r][16v + 8h ..+7]
+        const int64_t e0 = ((t0 + u) * 32 + r) * 32 + (DT == kF32 ? 16 * h + 4 * v : 16 * v + 8 * h);
+        // plain loads: a 128-B line is shared by the pieces of several lanes and
+        // load instructions, and nontemporal loads were slower (f32, 2 GiB: 0.82
+        // - 0.88 ms against 0.57 - 0.64 ms; bf16: 0.272 against 0.262 ms)
+        x[u][v] = full ? *reinterpret_cast<const mx_u32x4*>(src + e0 * ES)
+                       : load16_elems<ES>(src, e0, n);  // past n: zeros
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (t0 + u >= ntiles) break;
+      floatx16 acc = {};
+      if constexpr (DT == kF32) {
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hada(16 * h + t, r),
+                                                     __uint_as_float(x[u][t >> 2][t & 3]), acc, 0, 0, 0);
+      } else {
+        acc = mfma16<DT>(hada_frag16<DT>(8 * h, r), __builtin_bit_cast(hs_i16x8, x[u][0]), acc);
+        acc = mfma16<DT>(hada_frag16<DT>(16 + 8 * h, r), __builtin_bit_cast(hs_i16x8, x[u][1]), acc);
+      }
+      uint32_t sb, lo, hi;
+      fp4h_encode(acc, sb, lo, hi);
+      const int64_t group = (t0 + u) * 32 + r;
+      if (full) {
+        mx_u32x2 w;
+        w.x = lo;
+        w.y = hi;
+        __builtin_nontemporal_store(w, reinterpret_cast<mx_u32x2*>(out + group * 16 + 8 * h));
+        // byte (r & 3) of the quad's word, OR-ed over the quad
+        uint32_t s4 = sb << (8 * (r & 3));
+        s4 |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(s4), 0xB1, 0xF, 0xF, false));
+        s4 |= static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(s4), 0x4E, 0xF, 0xF, false));
+        if (h == 0 && (r & 3) == 0)
+          __builtin_nontemporal_store(s4, reinterpret_cast<uint32_t*>(scales + group));
+      } else if (group < nblocks) {
+        if (h == 0) scales[group] = static_cast<uint8_t>(sb);
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+          out[group * 16 + 8 * h + b] = static_cast<uint8_t>((b < 4 ? lo : hi) >> (8 * (b & 3)));
+      }
+    }
+  }
+}
+
+// 8 e2m1 codes (one payload word, code j in nibble j) -> 8 bf16, exact
+__device__ __forceinline__ hs_i16x8 fp4x8_to_bf16x8(uint32_t w) {
+  mx_f32x2 p[4];  // the byte select must be an immediate
+  p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 0);
+  p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 1);
+  p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 2);
+  p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 3);
+  hs_i16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = static_cast<short>(__float_as_uint(p[j >> 1][j & 1]) >> 16);
+  return o;
+}
+
+// `q` holds 16 * nblocks bytes, `scales` nblocks; writes dst[0 .. n)
+template <int DT, int U>
+__global__ void __launch_bounds__(kBlock)
+hs_mxfp4_hadamard_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scales,
+                          int64_t n, int64_t nblocks, char* __restrict__ dst) {
+  constexpr int DES = (DT == kF32) ? 4 : (DT == kF64 ? 8 : 2);
+  const int lane = threadIdx.x & 63;
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t ntiles = (nblocks + 31) / 32;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const hs_i16x8 b0 = hada_frag16<kBF16>(16 * h, r), b1 = hada_frag16<kBF16>(16 * h + 8, r);
+  const bool aligned = (reinterpret_cast<uintptr_t>(q) & 7) == 0 &&
+                       (reinterpret_cast<uintptr_t>(scales) & 3) == 0 &&
+                       (reinterpret_cast<uintptr_t>(dst) & (DES == 2 ? 7 : DES - 1)) == 0;
+  for (int64_t t0 = wave0 * U; t0 < ntiles; t0 += nwaves * U) {
+    const bool full = aligned && (t0 + U) * 1024 <= n;
+    uint32_t raw[U][2];
+    uint32_t sc[U][4];  // byte j of sc[u][g]: the scale of group 8g + 4h + j of tile u
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t g0 = (t0 + u) * 32;
+      const uint8_t* p = q + (g0 + r) * 16 + 8 * h;
+      if (full) {
+        const mx_u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const mx_u32x2*>(p));
+        raw[u][0] = w.x;
+        raw[u][1] = w.y;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          sc[u][g] = *reinterpret_cast<const uint32_t*>(scales + g0 + 8 * g + 4 * h);
+      } else {
+        raw[u][0] = raw[u][1] = 0;
+        if (g0 + r < nblocks) {
+#pragma unroll
+          for (int b = 0; b < 8; ++b) raw[u][b >> 2] |= uint32_t(p[b]) << (8 * (b & 3));
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          sc[u][g] = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int64_t group = g0 + 8 * g + 4 * h + j;
+            if (group < nblocks) sc[u][g] |= uint32_t(scales[group]) << (8 * j);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t tile = t0 + u;
+      if (tile >= ntiles) break;
+      floatx16 acc = {};
+      acc = mfma16<kBF16>(fp4x8_to_bf16x8(raw[u][0]), b0, acc);
+      acc = mfma16<kBF16>(fp4x8_to_bf16x8(raw[u][1]), b1, acc);
+      float f[16];  // register i: group (i&3) + 8(i>>2) + 4h, element r
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t sb = (sc[u][i >> 2] >> (8 * (i & 3))) & 0xffu;
+        f[i] = sb == kE8m0Nan ? __builtin_nanf("") : ldexpf(acc[i], int(sb) - 127 - 5);
+      }
+      if (full && DES == 2) {
+        if constexpr (DES == 2) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            hada_store_quad16(pack16<DT>(f[4 * g], f[4 * g + 1]), pack16<DT>(f[4 * g + 2], f[4 * g + 3]),
+                              r, dst + (tile * 32 + 8 * g + 4 * h) * 64);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int64_t e = (tile * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r;
+          if (full || e < n) store_from_f32(dst + e * DES, DT, f[i]);
         }
       }
     }
@@ -1260,6 +1521,36 @@ int hsg_mxfp4_dequantize(int dev, const void* q, const void* scales, int64_t n, 
     return launch(hs_mxfp4_dequant<decltype(dt)::value>, grid, stream, q, scales, n, dst);
   });
   return rc == kNoKernel ? unsupported_dtype("mxfp4 dest", dst_dtype) : rc;
+}
+
+// Hadamard-rotated MXFP4: src (bf16/f16/f32, contiguous, n elements) -> out
+// [n_pad / 2 bytes of e2m1 nibbles] + scales [n_pad / 32 E8M0 bytes], n_pad =
+// round_up(n, 32).  Every output byte is written.
+int hsg_mxfp4_hadamard_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out,
+                                void* scales, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  const int64_t nblocks = (n + 31) / 32;
+  const int rc = for_dtype<false>(src_dtype, [&](auto dt) {
+    constexpr int kDt = decltype(dt)::value;
+    constexpr int kU = kFp4hQuantU;
+    return launch(hs_mxfp4_hadamard_quant<kDt, kU>, grid_for(nblocks * 32, 1024 * kU, 256 * 8),
+                  stream, src, n, nblocks, out, scales);
+  });
+  return rc == kNoKernel ? unsupported_dtype("mxfp4 hadamard source", src_dtype) : rc;
+}
+
+int hsg_mxfp4_hadamard_dequantize(int dev, const void* q, const void* scales, int64_t n,
+                                  void* dst, int dst_dtype, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  const int64_t nblocks = (n + 31) / 32;
+  const int grid = grid_for(nblocks * 32, 1024 * kFp4hDequantU, 256 * 8);
+  const int rc = for_dtype<true>(dst_dtype, [&](auto dt) {
+    return launch(hs_mxfp4_hadamard_dequant<decltype(dt)::value, kFp4hDequantU>, grid, stream, q,
+                  scales, n, nblocks, dst);
+  });
+  return rc == kNoKernel ? unsupported_dtype("mxfp4 hadamard dest", dst_dtype) : rc;
 }
 
 // Hadamard-rotated fp8: payload `out` has n_pad = round_up(n, 32) bytes,

@@ -16,7 +16,8 @@ docs/getting_started.md): the reference's five, then
 * restore: ``NATIVE_RESTORE``, ``TRUST_OBJECTS``;
 * distributed: ``REBALANCE``, ``STATE_DICT_BARRIERS``, ``FORCE_COLLECTIVES``;
 * host: ``NUMA_BIND``, ``PINNED_POOL_MAX_BYTES``;
-* format: ``FP8_FORMAT`` (``mx`` | ``block`` | ``hadamard32`` | ``mxfp4``);
+* format: ``FP8_FORMAT`` (``mx`` | ``block`` | ``hadamard32`` | ``mxfp4`` |
+  ``mxfp4_hadamard32``);
 * tracing: ``TIMELINE``, ``ROCTX``.
 
 Everything else that used to be an environment switch -- engine sizing,
@@ -612,9 +613,11 @@ def fp8_format() -> str:
     """Layout of ``quantize=`` blobs: ``mx`` (default: e4m3fn + E8M0 scale
     per 32 elements), ``block`` (fp32 scale per 128), ``hadamard32`` (32-wide
     Hadamard rotation on the matrix cores, then fp32-scale blocks), ``mxfp4``
-    (e2m1 nibbles + E8M0 scale per 32 elements: 4.25 bits per element)."""
+    (e2m1 nibbles + E8M0 scale per 32 elements: 4.25 bits per element),
+    ``mxfp4_hadamard32`` (the same blob size, every block of 32 rotated by the
+    32-wide Hadamard matrix first: lower error on heavy-tailed tensors)."""
     v = str(_get("FP8_FORMAT") or "mx").strip().lower()
-    return v if v in ("mx", "block", "hadamard32", "mxfp4") else "mx"
+    return v if v in ("mx", "block", "hadamard32", "mxfp4", "mxfp4_hadamard32") else "mx"
 
 
 def plan_settings() -> tuple:

@@ -263,6 +263,10 @@ HSGPU_ABI = {
     "hsg_mxfp4_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "hsg_mxfp4_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                      c_void_p]),
+    "hsg_mxfp4_hadamard_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                            c_void_p]),
+    "hsg_mxfp4_hadamard_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                              c_void_p]),
     "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
                                    c_int, c_int, c_int, c_int, P(c_int)]),
     "hsg_drain_wait": (c_int, [c_void_p, P(c_uint64), P(c_uint64), c_char_p, P(c_double)]),
@@ -888,6 +892,42 @@ def mxfp4_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch
     assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
     _check(lib.hsg_mxfp4_dequantize(dev, q.data_ptr(), scales.data_ptr(), n, dst.data_ptr(),
                                     dtype_code(dst.dtype), stream_handle), "hsg_mxfp4_dequantize")
+
+
+def mxfp4_hadamard_tiles(dtype: torch.dtype, restore: bool = False) -> int:
+    """1024-element tiles one wave of hs_mxfp4_hadamard_quant (``dtype`` the
+    source's) / hs_mxfp4_hadamard_dequant takes per step (csrc/hsquant.hip
+    kFp4hQuantU, kFp4hDequantU)."""
+    return 2
+
+
+def mxfp4_hadamard_quantize(dev: int, src: torch.Tensor, out: torch.Tensor, scales: torch.Tensor,
+                            stream_handle: int) -> None:
+    """Hadamard-rotated MXFP4 (hs_mxfp4_hadamard_quant): every group of 32 is
+    rotated and is one MX block; ``out`` gets 16 bytes and ``scales`` one byte
+    per group of the tensor zero-padded to a multiple of 32."""
+    lib = require_gpu_lib()
+    n = src.numel()
+    nblocks = (n + 31) // 32
+    assert src.is_contiguous() and dtype_code(src.dtype) in (10, 11, 12)
+    assert out.numel() >= 16 * nblocks and scales.numel() >= nblocks
+    assert out.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _check(lib.hsg_mxfp4_hadamard_quantize(dev, src.data_ptr(), dtype_code(src.dtype), n,
+                                           out.data_ptr(), scales.data_ptr(), stream_handle),
+           "hsg_mxfp4_hadamard_quantize")
+
+
+def mxfp4_hadamard_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch.Tensor,
+                              stream_handle: int) -> None:
+    lib = require_gpu_lib()
+    n = dst.numel()
+    nblocks = (n + 31) // 32
+    assert dst.is_contiguous() and dtype_code(dst.dtype) in (10, 11, 12, 13)
+    assert q.numel() >= 16 * nblocks and scales.numel() >= nblocks
+    assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _check(lib.hsg_mxfp4_hadamard_dequantize(dev, q.data_ptr(), scales.data_ptr(), n,
+                                             dst.data_ptr(), dtype_code(dst.dtype), stream_handle),
+           "hsg_mxfp4_hadamard_dequantize")
 
 
 # hsg_drain_start `flags` and the buffers hsg_drain_wait / hsg_restore_wait

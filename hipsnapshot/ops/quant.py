@@ -105,6 +105,52 @@ either side equals ``mxfp4_dequantize_reference`` bit for bit.
 Measured relative L2 error ``|restored - x| / |x|`` of the CPU references on
 2^20 seeded values: N(0, 1): ``mxfp4`` 0.1155, ``mx`` 0.0266; Student-t(2):
 ``mxfp4`` 0.1239, ``mx`` 0.0262.
+
+Rotated MXFP4 layout (opt-in, ``HIPSNAPSHOT_FP8_FORMAT=mxfp4_hadamard32``):
+MXFP4 whose blocks are Hadamard-rotated groups, the same 4.25 bits per
+element::
+
+    {"format": "fp4_e2m1_mx", "block": 32, "scale": "e8m0", "rotation": "hadamard32",
+     "orig_dtype": ..., "payload_bytes": P = n_pad / 2, "nblocks": B = n_pad / 32,
+     "total_bytes": P + B}      with n_pad = round_up(n, 32)
+
+blob = ``[P payload bytes][B E8M0 bytes]``.  One outlier pushes the other 31
+values of an e2m1 block to the bottom of an 8-magnitude grid; the rotation
+spreads it over exactly the 32 elements that share the scale byte.  The rules,
+shared by ``hs_mxfp4_hadamard_quant`` / ``hs_mxfp4_hadamard_dequant`` and the
+references below (test ``is_mxfp4_hadamard`` before ``is_mxfp4``, which looks
+at ``format`` only):
+
+* the flat tensor, zero-padded to ``n_pad``, is cut into groups of 32 and group
+  ``g`` is rotated, ``y = x_g H`` with ``H = hadamard_matrix()``, the sums in
+  fp32 in ``HADAMARD_K_ORDER`` (``_rotate_sequential``);
+* the 32 rotated values of a group are one MX block: scale and codes follow the
+  ``mxfp4`` rules on ``y`` (``k``, clamp, ties to the even index, sign kept on
+  zero, nibble order);
+* stricter than ``mxfp4`` on non-finite values: if any rotated value of a group
+  is inf or NaN -- an input inf (it makes every rotated value +-inf, and code
+  +-6 would restore finite garbage), an input NaN, or an fp32 overflow of a
+  sum -- the group stores scale byte ``0xFF`` and 16 zero bytes and restores
+  as 32 positive quiet NaNs, as a non-finite input spoils its own row of 32 in
+  the rotated fp8 format;
+* restore is ``x = (Q H) * 2^(k - 5)``: a row sum of e2m1 values is a multiple
+  of 0.5 of magnitude <= 192, exact in fp32 in any order, the product with the
+  power of two is one fp32 operation, then one rounding to the target dtype.
+  So a blob restores to the same bits on the CPU and on the GPU for every
+  target dtype.
+
+A CPU take and a GPU take of an fp32 tensor write identical bytes.  bf16 / f16
+tensors go through the 16-bit MFMA, which sums in the hardware's order: a
+rotated value can differ from the k-ordered reference in its last fp32 bit and
+a code exactly on a rounding boundary can move -- the known gap of
+``hadamard32`` (``docs/next_steps.md``), far rarer for e2m1 (other summation
+orders on the CPU moved at most 1 code in 2^20 and no scale byte).
+
+Measured relative L2 error of the CPU references on 2^20 seeded values,
+``mxfp4`` / ``mxfp4_hadamard32``: N(0, 1) 0.1154 / 0.1184; Student-t(2) 0.1327 /
+0.1011; Student-t(3) 0.1505 / 0.1129; Student-t(5) 0.1327 / 0.1151; Laplace
+0.1322 / 0.1151; N(0, 1) with every 257th value x50: 0.1361 / 0.1050.  About a
+quarter lower on heavy tails, 2.6 % higher on pure Gaussians.
 """
 
 from __future__ import annotations
@@ -159,6 +205,11 @@ def is_mxfp4(info: Dict[str, Any]) -> bool:
     return info.get("format") == "fp4_e2m1_mx"
 
 
+def is_mxfp4_hadamard(info: Dict[str, Any]) -> bool:
+    """Test this before ``is_mxfp4``, which looks at ``format`` only."""
+    return is_mxfp4(info) and info.get("rotation") == "hadamard32"
+
+
 def mxfp4_payload_bytes(n: int) -> int:
     return _round_up((n + 1) // 2, 16)
 
@@ -174,10 +225,15 @@ def _round_up(n: int, m: int) -> int:
 
 def fp8_entry_quant_info(t: torch.Tensor, vpt: int = DEFAULT_VPT,
                          rotation: str = None) -> Dict[str, Any]:
-    rotation = rotation or default_rotation()
-    n = t.numel()
     from .. import knobs
 
+    n = t.numel()
+    if rotation in (None, "hadamard32") and knobs.fp8_format() == "mxfp4_hadamard32":
+        nblocks = _round_up(n, GROUP) // GROUP  # block = rotated group
+        return {"format": "fp4_e2m1_mx", "block": MX_BLOCK, "scale": "e8m0",
+                "rotation": "hadamard32", "orig_dtype": dtype_to_string(t.dtype),
+                "payload_bytes": 16 * nblocks, "nblocks": nblocks, "total_bytes": 17 * nblocks}
+    rotation = rotation or default_rotation()
     if rotation == "none" and knobs.fp8_format() == "mxfp4":
         payload = mxfp4_payload_bytes(n)
         nblocks = (n + MX_BLOCK - 1) // MX_BLOCK
@@ -375,6 +431,41 @@ def _rotate_sequential(rows: torch.Tensor) -> torch.Tensor:
     return acc
 
 
+def mxfp4_hadamard_quantize_reference(x: torch.Tensor):
+    """Rotated MXFP4 reference: returns (payload[n_pad / 2] uint8, scale
+    bytes[n_pad / 32] uint8), n_pad = round_up(n, 32).  Each group of 32 is
+    rotated (fp32 sums in ``HADAMARD_K_ORDER``) and is one MX block under the
+    ``mxfp4`` rules; a group with a non-finite rotated value stores ``0xFF`` and
+    zeros (module docstring)."""
+    flat = x.detach().reshape(-1).float()
+    n = flat.numel()
+    rows = torch.zeros(_round_up(n, GROUP) // GROUP, GROUP, dtype=torch.float32,
+                       device=flat.device)
+    rows.view(-1)[:n] = flat
+    y = _rotate_sequential(rows)
+    bad = ~torch.isfinite(y).all(dim=1)
+    y[bad] = float("nan")  # the mxfp4 rule for a block with a NaN: 0xFF and zeros
+    return mxfp4_quantize_reference(y)
+
+
+def mxfp4_hadamard_dequantize_reference(payload: torch.Tensor, sbytes: torch.Tensor, n: int,
+                                        dtype: torch.dtype) -> torch.Tensor:
+    """``x = (Q H) * 2^(k - 5)``: the row sums of e2m1 values are multiples of
+    0.5 of magnitude <= 192 (float64 matmul, exact in fp32), one fp32 product
+    with the power of two, one rounding to ``dtype``; a group with the NaN
+    scale byte restores as positive quiet NaNs."""
+    nblocks = sbytes.numel()
+    is_nan = sbytes == E8M0_NAN
+    ones = torch.full_like(sbytes, 127)  # decode the codes alone: scale 2^0
+    q = mxfp4_dequantize_reference(payload, ones, nblocks * GROUP, torch.float32)
+    z = (q.view(nblocks, GROUP).double() @ hadamard_matrix(GROUP, q.device).double()).float()
+    k = torch.where(is_nan, ones, sbytes).to(torch.int32) - 127 - 5
+    out = (z * pow2(k)[:, None]).reshape(-1)[:n].to(dtype)
+    view, bits = _QUIET_NAN_BITS[dtype]
+    out.view(view)[is_nan.repeat_interleave(GROUP)[:n]] = bits
+    return out
+
+
 def hadamard_quantize_reference(x: torch.Tensor, block: int = 128):
     """Returns (q[n_pad] e4m3fn, scale[nblocks]) with n_pad = round_up(n, 32)."""
     flat = x.detach().reshape(-1).float()
@@ -449,9 +540,11 @@ def stage_fp8(t: torch.Tensor, entry: TensorEntry, producer: int) -> StagedBuffe
 
 
 def _stage_mx(t: torch.Tensor, info: Dict[str, Any], producer: int) -> StagedBuffer:
-    """The two E8M0 layouts: MX fp8 and MXFP4 (same blob shape, other kernel)."""
+    """The E8M0 layouts: MX fp8, MXFP4 and rotated MXFP4 (same blob shape,
+    other kernel)."""
     payload, total = info["payload_bytes"], info["total_bytes"]
-    fp4 = is_mxfp4(info)
+    fp4h = is_mxfp4_hadamard(info)
+    fp4 = is_mxfp4(info) and not fp4h
     if t.is_cuda:
         from ..engine import staging
         from . import native
@@ -465,10 +558,12 @@ def _stage_mx(t: torch.Tensor, info: Dict[str, Any], producer: int) -> StagedBuf
             stream.wait_event(ev)
         src = t if t.is_contiguous() else t.contiguous()
         blob = torch.empty(total, dtype=torch.uint8, device=t.device)  # kernel writes all of it
-        quantize = native.mxfp4_quantize if fp4 else native.mx8_quantize
+        quantize = (native.mxfp4_hadamard_quantize if fp4h else
+                    native.mxfp4_quantize if fp4 else native.mx8_quantize)
         quantize(dev, src, blob[:payload], blob[payload:], int(stream.cuda_stream))
         return staging.d2h_tensor(blob, int(stream.cuda_stream))
-    q, sbytes = mxfp4_quantize_reference(t) if fp4 else mx_quantize_reference(t)
+    q, sbytes = (mxfp4_hadamard_quantize_reference(t) if fp4h else
+                 mxfp4_quantize_reference(t) if fp4 else mx_quantize_reference(t))
     blob = torch.zeros(total, dtype=torch.uint8)
     blob[: q.numel()] = q.view(torch.uint8)
     blob[payload:] = sbytes
@@ -497,7 +592,9 @@ def dequantize_host_fp8(buf, entry: TensorEntry) -> torch.Tensor:
     dtype = string_to_dtype(entry.dtype)
     if is_mxfp4(info):
         p = info["payload_bytes"]
-        out = mxfp4_dequantize_reference(raw[:p], raw[p: p + info["nblocks"]], n, dtype)
+        decode = (mxfp4_hadamard_dequantize_reference if is_mxfp4_hadamard(info)
+                  else mxfp4_dequantize_reference)
+        out = decode(raw[:p], raw[p: p + info["nblocks"]], n, dtype)
         return out.view(list(entry.shape))
     if is_mx(info):
         p = info["payload_bytes"]
@@ -523,7 +620,9 @@ def dequantize_device(blob_dev: torch.Tensor, entry: TensorEntry, dst: torch.Ten
     dev = dst.device.index or 0
     if is_mxfp4(info):
         p = info["payload_bytes"]
-        native.mxfp4_dequantize(dev, blob_dev[:p], blob_dev[p: p + info["nblocks"]], dst, stream)
+        decode = (native.mxfp4_hadamard_dequantize if is_mxfp4_hadamard(info)
+                  else native.mxfp4_dequantize)
+        decode(dev, blob_dev[:p], blob_dev[p: p + info["nblocks"]], dst, stream)
         return
     if is_mx(info):
         p = info["payload_bytes"]

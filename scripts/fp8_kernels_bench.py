@@ -1,13 +1,15 @@
 """fp8 quantize / dequantize kernels alone on 512 Mi elements (1 GiB of bf16;
 for rocprofv3 --stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128,
-MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32).  Prints one JSON line per
+MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32), Hadamard-rotated MXFP4.
+Prints one JSON line per
 kernel with host-timed GB/s of HBM traffic (read + written bytes), the time
 between device events around the call, and GB/s of the tensor alone (source
 bytes of a quantize, destination bytes of a dequantize).
 
     fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [mode ...]
 
-Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``.  ``--rounds R`` goes
+Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``, ``mxfp4_hadamard32``.
+``--rounds R`` goes
 through the list of modes R times, so that two modes alternate and the spread
 of one mode's repeats is seen beside the difference between the two.
 
@@ -62,9 +64,9 @@ def main():
     for mode in modes:
         if mode == "mx_e8m0":
             info = quant.fp8_entry_quant_info(w, rotation="none")
-        elif mode == "mxfp4":
-            os.environ["HIPSNAPSHOT_FP8_FORMAT"] = "mxfp4"
-            info = quant.fp8_entry_quant_info(w, rotation="none")
+        elif mode in ("mxfp4", "mxfp4_hadamard32"):
+            os.environ["HIPSNAPSHOT_FP8_FORMAT"] = mode
+            info = quant.fp8_entry_quant_info(w, rotation=None if "hadamard" in mode else "none")
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         else:
             os.environ["HIPSNAPSHOT_FP8_FORMAT"] = "block"
@@ -72,7 +74,8 @@ def main():
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         blob = torch.zeros(info["total_bytes"], dtype=torch.uint8, device="cuda:0")
         p = info["payload_bytes"]
-        sc = blob[p:] if mode in ("mx_e8m0", "mxfp4") else blob[p:].view(torch.float32)
+        e8m0 = mode in ("mx_e8m0", "mxfp4", "mxfp4_hadamard32")
+        sc = blob[p:] if e8m0 else blob[p:].view(torch.float32)
         back = torch.empty(nw + off, dtype=dtype, device="cuda:0")[off:]
         if mode == "mx_e8m0":
             q = lambda: native.mx8_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
@@ -80,6 +83,9 @@ def main():
         elif mode == "mxfp4":
             q = lambda: native.mxfp4_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mxfp4_dequantize(dev, blob[:p], sc, back, hs)  # noqa: E731
+        elif mode == "mxfp4_hadamard32":
+            q = lambda: native.mxfp4_hadamard_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
+            dq = lambda: native.mxfp4_hadamard_dequantize(dev, blob[:p], sc, back, hs)  # noqa
         elif mode == "none":
             q = lambda: native.fp8_quantize(dev, w, blob[:p], sc, info["vpt"], hs)  # noqa: E731
             dq = lambda: native.fp8_dequantize(dev, blob[:nw], sc, back, info["vpt"], hs)  # noqa
