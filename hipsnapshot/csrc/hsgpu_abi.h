@@ -82,7 +82,7 @@ int hsg_hash64(int dev, int slot, int after_slot, const void* p, uint64_t n, uin
 int hsg_hash64_result(int dev, int slot, int handle, uint64_t* out);
 int hsg_hash64_batch(int dev, void* stream, const void* descs, int n, uint64_t* sums_out);
 
-// hsquant.hip: fp8 / MX8 / MXFP4 quantization
+// hsquant.hip: fp8 / MX8 / MXFP4 / MXFP6 quantization
 int hsg_fp8_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out, void* scales,
                      int vpt, void* stream);
 int hsg_fp8_dequantize(int dev, const void* q, const void* scales, int64_t n, void* dst,
@@ -103,6 +103,10 @@ int hsg_mxfp4_hadamard_quantize(int dev, const void* src, int src_dtype, int64_t
                                 void* scales, void* stream);
 int hsg_mxfp4_hadamard_dequantize(int dev, const void* q, const void* scales, int64_t n,
                                   void* dst, int dst_dtype, void* stream);
+int hsg_mxfp6_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out,
+                       void* scales, void* stream);
+int hsg_mxfp6_dequantize(int dev, const void* q, const void* scales, int64_t n, void* dst,
+                         int dst_dtype, void* stream);
 
 // hsgpu.hip: managed memory, stream gate
 int hsg_is_managed(const void* p);

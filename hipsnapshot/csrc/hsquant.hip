@@ -2,7 +2,9 @@
 // blockwise OCP-fp8 (e4m3fn) with an f32 scale per block, MX fp8 (one E8M0
 // scale byte per 32 elements), Hadamard-rotated fp8 on the matrix cores and
 // MXFP4 (e2m1 nibbles, one E8M0 scale byte per 32 elements, gfx950's scaled
-// fp4 conversions) -- and their hsg_*quantize / hsg_*dequantize entry points.
+// fp4 conversions) and MXFP6 (e2m3 codes, 32 in 24 bytes, the same scale, a
+// whole block per conversion) -- and their hsg_*quantize / hsg_*dequantize
+// entry points.
 // Wave size is 64.
 
 #include <algorithm>
@@ -487,9 +489,11 @@ __device__ __forceinline__ uint32_t fp4_lane_key(const mx_u32x4& w, bool& nonfin
   return a;
 }
 
-// E8M0 byte of a block from its amax key (finite pattern or kFp4NanKey)
+// E8M0 byte of a block from its amax key (finite pattern or kFp4NanKey), for
+// the element formats whose largest magnitude is in [4, 8): frexp gives amax =
+// m 2^e, and `top` is that magnitude / 8 (e2m1: 0.75, e2m3: 0.9375)
 template <int DT>
-__device__ __forceinline__ uint32_t mxfp4_scale_byte(uint32_t key) {
+__device__ __forceinline__ uint32_t mxfp4_scale_byte(uint32_t key, float top = 0.75f) {
   if (key == kFp4NanKey) return kE8m0Nan;
   float amax;
   if constexpr (DT == kF32) amax = __uint_as_float(key);
@@ -498,7 +502,7 @@ __device__ __forceinline__ uint32_t mxfp4_scale_byte(uint32_t key) {
   if (amax > 0.f) {
     int e;
     const float m = frexpf(amax, &e);
-    k = (m <= 0.75f) ? e - 3 : e - 2;
+    k = (m <= top) ? e - 3 : e - 2;
     k = k < -127 ? -127 : (k > 127 ? 127 : k);
   }
   return static_cast<uint32_t>(k + 127);
@@ -631,20 +635,23 @@ hs_mxfp4_quant(const char* __restrict__ src, int64_t n, int64_t payload,
 // 16 B of restored output (8 x bf16/f16, 4 x f32 or 2 x f64), written once
 // and not read again by this kernel: a nontemporal store
 template <int DT>
-__device__ __forceinline__ void fp4_store16(char* p, const float* f) {
-  mx_u32x4 w;
+__device__ __forceinline__ mx_u32x4 fp4_piece16(const float* f) {
   if constexpr (DT == kF32) {
-    w = mx_u32x4{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
-                 __float_as_uint(f[3])};
+    return mx_u32x4{__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]),
+                    __float_as_uint(f[3])};
   } else if constexpr (DT == kF64) {
     const uint64_t a = __builtin_bit_cast(uint64_t, static_cast<double>(f[0]));
     const uint64_t b = __builtin_bit_cast(uint64_t, static_cast<double>(f[1]));
-    w = mx_u32x4{uint32_t(a), uint32_t(a >> 32), uint32_t(b), uint32_t(b >> 32)};
+    return mx_u32x4{uint32_t(a), uint32_t(a >> 32), uint32_t(b), uint32_t(b >> 32)};
   } else {
-    w = mx_u32x4{pack16<DT>(f[0], f[1]), pack16<DT>(f[2], f[3]), pack16<DT>(f[4], f[5]),
-                 pack16<DT>(f[6], f[7])};
+    return mx_u32x4{pack16<DT>(f[0], f[1]), pack16<DT>(f[2], f[3]), pack16<DT>(f[4], f[5]),
+                    pack16<DT>(f[6], f[7])};
   }
-  __builtin_nontemporal_store(w, reinterpret_cast<mx_u32x4*>(p));
+}
+
+template <int DT>
+__device__ __forceinline__ void fp4_store16(char* p, const float* f) {
+  __builtin_nontemporal_store(fp4_piece16<DT>(f), reinterpret_cast<mx_u32x4*>(p));
 }
 
 template <int DT>
@@ -699,6 +706,307 @@ hs_mxfp4_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scal
       } else {
         for (int j = 0; j < EPL && e0 + j < n; ++j) store_from_f32(dst + (e0 + j) * DES, DT, f[j]);
       }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// MXFP6 (format "fp6_e2m3_mx"): e2m3 codes -- sign in bit 5, exponent in bits
+// 4-3 (bias 1), mantissa in bits 2-0: magnitudes 0 .. 1.875 in steps of 1/8,
+// 2 .. 3.75 in steps of 1/4, 4 .. 7.5 in steps of 1/2 -- and one E8M0 scale
+// byte k + 127 per 32 elements.  Block b is payload bytes [24 b, 24 b + 24)
+// read as a little-endian 192-bit string, element j its bits [6 j, 6 j + 6).
+// The rules are MXFP4's with the other grid (ops/quant.py
+// mxfp6_quantize_reference applies the same ones): k is the smallest exponent
+// with amax <= 7.5 * 2^k over the finite elements (frexp: k = e - 3 if m <=
+// 0.9375 else e - 2), ties go to the even index, the sign is kept on zero,
+// +-inf is code +-7.5 and sets no scale, a block with a NaN stores 0xFF and 24
+// zero bytes and restores as positive quiet NaNs, restore is q * 2^k in f32
+// and one rounding.  payload = round_up(24 * nblocks, 16) bytes; elements
+// from n on are code 0 and the bytes past the last block are zero.
+//
+// gfx950 converts a whole block in one instruction (v_cvt_scalef32_pk32_fp6_
+// {bf16,f16}, v_cvt_scalef32_2xpk16_fp6_f32, v_cvt_scalef32_pk32_f32_fp6), so
+// here a LANE owns a block, where the fp8 and fp4 streams spread one over 4 or
+// 8 lanes: a wave step is 64 blocks, 2048 elements, and turns into 1536
+// contiguous payload bytes and 64 contiguous scale bytes.
+//   * amax is the unsigned max of the |x| bit patterns of the lane's own 16 or
+//     32 registers (fp4_lane_key per 16 B): no shuffle;
+//   * per lane the results would be 24 B at a 24-B stride (quantize) or 64 /
+//     128 / 256 B at that stride (dequantize), and strided 16-B stores cost the
+//     rotated MXFP4 restore a factor of 2.3 to 3.3 (docs/architecture.md
+//     section 4).  So every result goes through the wave's own piece of LDS
+//     and every global store instruction covers one contiguous span: three
+//     8-B stores per lane for the payload, 16-B nontemporal stores for
+//     restored values, one 4-B store from every fourth lane for the scales
+//     (bytes gathered over the quad by two DPP moves);
+//   * LDS patterns: a lane writes its six payload dwords as three 8-B pieces
+//     at a stride of three such pieces, and its restored values as 16-B pieces
+//     in a row of NP + 1 pieces (NP = 4, 8 or 16 pieces of payload per lane).
+//     Both strides are odd in units of the access width, so the lanes of one
+//     instruction spread over all banks; a 6-dword stride with 4-B writes
+//     would put two lanes on each bank.  The reads are contiguous.  An f64
+//     destination goes in two passes of 32 lanes, so that it needs the LDS of
+//     an f32 one (about 9 KiB per wave) and its stores still cover a span;
+//   * a wave only ever touches its own LDS, whose instructions complete in
+//     order: wave_lds_fence() orders the compiler, no s_barrier is needed.
+// Loads are wave-contiguous as well: the source's 16-B pieces (and the
+// restore's 8-B payload pieces) go through the same LDS rows into block
+// ownership.  The other plan, every lane loading its own block at a 64- or
+// 128-B stride (and its 24 payload bytes at a 24-B stride) with no LDS on the
+// way in, was measured in the same build on 512 Mi elements and was slower in
+// all four cases: quantize bf16 0.276 ms against 0.267, f32 0.482 against
+// 0.474; restore bf16 0.281 against 0.278, f32 0.485 against 0.477 (medians;
+// profiles/mxfp6_kernels/strided_loads_*.jsonl, docs/architecture.md section
+// 4).
+// Found on an MI355X with a probe of the four conversions and by tests/
+// test_gpu_mxfp6.py: element j of a block lands in bits [6 j, 6 j + 6) of the
+// six result registers, for the 16-bit sources and for the decode;
+// v_cvt_scalef32_2xpk16_fp6_f32 interleaves its operands (element 2 i from the
+// first, 2 i + 1 from the second); ties go to the even code, subnormal codes
+// and sources and the scale field 0 (k = -127) are exact, a zero result keeps
+// its sign, larger magnitudes and inf saturate to +-7.5, a NaN becomes +7.5.
+// As for fp4 only inf (by rule, not by need) and the NaN block are patched.
+// The scale operand is an f32 of which only the exponent field, the E8M0
+// byte, is read.
+// A misaligned source, payload, scale array or destination (wave-uniform
+// test) and the tail chunk take the element path: the lane still owns its
+// block, reads it element by element (zeros from n on) and writes its bytes
+// one by one; the lane of the last block also zeroes the bytes up to `payload`.
+// ---------------------------------------------------------------------------
+
+constexpr int kFp6Step = 64 * 32;  // elements of a wave step: one block per lane
+
+typedef unsigned int mx_u32x6 __attribute__((ext_vector_type(6)));
+typedef unsigned int mx_u32x16 __attribute__((ext_vector_type(16)));
+typedef float mx_f32x16 __attribute__((ext_vector_type(16)));
+typedef float mx_f32x32 __attribute__((ext_vector_type(32)));
+typedef __bf16 mx_bf16x32 __attribute__((ext_vector_type(32)));
+typedef _Float16 mx_f16x32 __attribute__((ext_vector_type(32)));
+
+// between a wave's LDS writes and its reads of what other lanes wrote
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the six payload dwords of a lane's block (NP 16-B pieces `w`) under scale
+// byte `sb`.  The conversions divide by 2^(exponent field of `scale`) and
+// round to nearest even.  Patched after them: the code of an inf (sign | 31)
+// and the all-zero payload of a NaN block.
+// A block conversion writes its result registers before it has read all of
+// its operands, and this compiler does not keep the two apart: the f32
+// quantizer came out as `v_cvt_scalef32_2xpk16_fp6_f32 v[32:37], v[0:15],
+// v[16:31], v32` and gave garbage codes from the third element on.  The empty
+// asm after each conversion uses the operands once more, so they are live
+// across it and share no register with the result.
+template <int DT>
+__device__ __forceinline__ mx_u32x6 fp6_pack(const mx_u32x4* w, uint32_t sb, bool nonfinite) {
+  mx_u32x6 r = {0, 0, 0, 0, 0, 0};
+  if (sb == kE8m0Nan) return r;
+  const float scale = __uint_as_float(sb << 23);
+  constexpr int NW = (DT == kF32) ? 32 : 16;
+  uint32_t e[NW];  // scalars first (see fp4_pack)
+#pragma unroll
+  for (int j = 0; j < NW; ++j) e[j] = w[j >> 2][j & 3];
+  if constexpr (DT == kF32) {
+    // element 2 i of the result is element i of the first operand, element
+    // 2 i + 1 element i of the second
+    mx_f32x16 a, b;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      a[j] = __uint_as_float(e[2 * j]);
+      b[j] = __uint_as_float(e[2 * j + 1]);
+    }
+    r = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(a, b, scale);
+    asm volatile("" ::"v"(a), "v"(b), "v"(scale));  // no register shared with r (see above)
+  } else {
+    mx_u32x16 v;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = e[j];
+    if constexpr (DT == kBF16)
+      r = __builtin_amdgcn_cvt_scalef32_pk32_fp6_bf16(__builtin_bit_cast(mx_bf16x32, v), scale);
+    else
+      r = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(__builtin_bit_cast(mx_f16x32, v), scale);
+    asm volatile("" ::"v"(v), "v"(scale));  // no register shared with r (see above)
+  }
+  if (nonfinite) {
+    uint32_t c[6] = {r[0], r[1], r[2], r[3], r[4], r[5]};
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      uint32_t bits;
+      if constexpr (DT == kF32) bits = e[j];
+      else bits = (e[j >> 1] >> (16 * (j & 1))) << 16;  // as the f32's upper half
+      if ((bits & 0x7fffffffu) != (kInfBits<DT> << (DT == kF32 ? 0 : 16))) continue;
+      const uint32_t code = 31u | ((bits >> 31) << 5);
+      constexpr uint32_t kMask = 0x3fu;
+      const int wd = (6 * j) >> 5, sh = (6 * j) & 31;
+      c[wd] = (c[wd] & ~(kMask << sh)) | (code << sh);
+      if (sh > 26) c[wd + 1] = (c[wd + 1] & ~(kMask >> (32 - sh))) | (code >> (32 - sh));
+    }
+    r = mx_u32x6{c[0], c[1], c[2], c[3], c[4], c[5]};
+  }
+  return r;
+}
+
+// `out` holds `payload` >= 24 * ceil(n / 32) bytes, `scales` ceil(n / 32)
+template <int DT>
+__global__ void __launch_bounds__(kBlock)
+hs_mxfp6_quant(const char* __restrict__ src, int64_t n, int64_t payload,
+               uint8_t* __restrict__ out, uint8_t* __restrict__ scales) {
+  constexpr int ES = (DT == kF32) ? 4 : 2;
+  constexpr int EPP = 16 / ES;     // elements per 16-B piece
+  constexpr int NP = 32 / EPP;     // pieces per block: 4 or 8
+  constexpr int ROW = NP + 1;      // LDS row of a block, in pieces
+  __shared__ mx_u32x4 lds_all[kBlock / 64][64 * ROW];  // source rows, then 1536 B of payload
+  mx_u32x4* lds = lds_all[threadIdx.x >> 6];
+  mx_u32x2* lds8 = reinterpret_cast<mx_u32x2*>(lds);
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const int64_t nblocks = (n + 31) / 32;
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(out) & 7) == 0 &&
+                       (reinterpret_cast<uintptr_t>(scales) & 3) == 0;
+  for (int64_t base = wave0 * kFp6Step; base < n; base += nwaves * kFp6Step) {
+    const bool full = aligned && base + kFp6Step <= n;
+    const int64_t blk = base / 32 + lane;
+    mx_u32x4 raw[NP];
+    if (full) {
+      const mx_u32x4* p = reinterpret_cast<const mx_u32x4*>(src + base * ES);
+      // wave-contiguous loads, then piece 64 i + lane to its block's row
+#pragma unroll
+      for (int i = 0; i < NP; ++i) raw[i] = __builtin_nontemporal_load(p + 64 * i + lane);
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const int q = 64 * i + lane;
+        lds[(q / NP) * ROW + (q % NP)] = raw[i];
+      }
+      wave_lds_fence();
+#pragma unroll
+      for (int i = 0; i < NP; ++i) raw[i] = lds[lane * ROW + i];
+      wave_lds_fence();
+    } else {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) raw[i] = load16_elems<ES>(src, blk * 32 + i * EPP, n);
+    }
+    uint32_t key = 0;
+    bool nonfinite = false;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      bool nf;
+      key = max(key, fp4_lane_key<DT>(raw[i], nf));
+      nonfinite |= nf;
+    }
+    const uint32_t sb = mxfp4_scale_byte<DT>(key, 0.9375f);
+    const mx_u32x6 code = fp6_pack<DT>(raw, sb, nonfinite);
+    const uint32_t c[6] = {code[0], code[1], code[2], code[3], code[4], code[5]};
+    if (full) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) lds8[3 * lane + i] = mx_u32x2{c[2 * i], c[2 * i + 1]};
+      wave_lds_fence();
+      mx_u32x2* o = reinterpret_cast<mx_u32x2*>(out + 24 * (base / 32));
+#pragma unroll
+      for (int i = 0; i < 3; ++i) __builtin_nontemporal_store(lds8[64 * i + lane], o + 64 * i + lane);
+      wave_lds_fence();
+      // the quad's four scale bytes into one word, stored by its first lane
+      uint32_t word = sb << (8 * (lane & 3));
+      word |= static_cast<uint32_t>(
+          __builtin_amdgcn_mov_dpp(static_cast<int>(word), 0xB1, 0xF, 0xF, false));  // lane ^ 1
+      word |= static_cast<uint32_t>(
+          __builtin_amdgcn_mov_dpp(static_cast<int>(word), 0x4E, 0xF, 0xF, false));  // lane ^ 2
+      if ((lane & 3) == 0)
+        __builtin_nontemporal_store(word,
+                                    reinterpret_cast<uint32_t*>(scales + base / 32) + (lane >> 2));
+    } else if (blk < nblocks) {
+      scales[blk] = static_cast<uint8_t>(sb);
+      const bool last = blk == nblocks - 1;
+#pragma unroll
+      for (int t = 0; t < 32; ++t) {
+        const int64_t at = 24 * blk + t;
+        if (t < 24) out[at] = static_cast<uint8_t>(c[t >> 2] >> (8 * (t & 3)));
+        else if (last && at < payload) out[at] = 0;
+      }
+    }
+  }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(kBlock)
+hs_mxfp6_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scales, int64_t n,
+                 char* __restrict__ dst) {
+  constexpr int DES = (DT == kF32) ? 4 : (DT == kF64 ? 8 : 2);
+  constexpr int EPP = 16 / DES;             // elements per 16-B piece
+  constexpr int NP = 32 / EPP;              // pieces per block: 4, 8 or 16
+  constexpr int PASSES = NP == 16 ? 2 : 1;  // f64: 32 lanes at a time
+  constexpr int LPP = 64 / PASSES;          // lanes per pass
+  constexpr int ROW = NP + 1;               // LDS row of a block, in pieces
+  __shared__ mx_u32x4 lds_all[kBlock / 64][LPP * ROW];
+  mx_u32x4* lds = lds_all[threadIdx.x >> 6];
+  mx_u32x2* lds8 = reinterpret_cast<mx_u32x2*>(lds);
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const int64_t nblocks = (n + 31) / 32;
+  const bool aligned = (reinterpret_cast<uintptr_t>(q) & 7) == 0 &&
+                       (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  for (int64_t base = wave0 * kFp6Step; base < n; base += nwaves * kFp6Step) {
+    const bool full = aligned && base + kFp6Step <= n;
+    const int64_t blk = base / 32 + lane;
+    uint32_t c[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t sb = 0;  // past n: nothing stored
+    if (full) {
+      const mx_u32x2* p = reinterpret_cast<const mx_u32x2*>(q + 24 * (base / 32));
+      sb = scales[blk];
+      mx_u32x2 t[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) t[i] = __builtin_nontemporal_load(p + 64 * i + lane);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) lds8[64 * i + lane] = t[i];
+      wave_lds_fence();
+#pragma unroll
+      for (int i = 0; i < 3; ++i) t[i] = lds8[3 * lane + i];
+      wave_lds_fence();
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        c[2 * i] = t[i].x;
+        c[2 * i + 1] = t[i].y;
+      }
+    } else if (blk < nblocks) {
+      sb = scales[blk];
+#pragma unroll
+      for (int t = 0; t < 24; ++t) c[t >> 2] |= uint32_t(q[24 * blk + t]) << (8 * (t & 3));
+    }
+    const mx_u32x6 cv = {c[0], c[1], c[2], c[3], c[4], c[5]};
+    const mx_f32x32 dec = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(cv, 1.0f);
+    asm volatile("" ::"v"(cv));  // no register shared with dec (see fp6_pack)
+    const int k = int(sb) - 127;
+    float f[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) f[j] = sb == kE8m0Nan ? __builtin_nanf("") : ldexpf(dec[j], k);
+    if (full) {
+#pragma unroll
+      for (int h = 0; h < PASSES; ++h) {
+        if (PASSES == 1 || lane / LPP == h) {
+#pragma unroll
+          for (int i = 0; i < NP; ++i) lds[(lane % LPP) * ROW + i] = fp4_piece16<DT>(f + i * EPP);
+        }
+        wave_lds_fence();
+        mx_u32x4* o = reinterpret_cast<mx_u32x4*>(dst + (base + h * LPP * 32) * DES);
+#pragma unroll
+        for (int i = 0; i < NP / PASSES; ++i) {
+          const int piece = 64 * i + lane;
+          __builtin_nontemporal_store(lds[(piece / NP) * ROW + (piece % NP)], o + piece);
+        }
+        wave_lds_fence();
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 32; ++j)
+        if (blk * 32 + j < n) store_from_f32(dst + (blk * 32 + j) * DES, DT, f[j]);
     }
   }
 }
@@ -1521,6 +1829,32 @@ int hsg_mxfp4_dequantize(int dev, const void* q, const void* scales, int64_t n, 
     return launch(hs_mxfp4_dequant<decltype(dt)::value>, grid, stream, q, scales, n, dst);
   });
   return rc == kNoKernel ? unsupported_dtype("mxfp4 dest", dst_dtype) : rc;
+}
+
+// MXFP6: src (bf16/f16/f32, contiguous, n elements) -> out [payload =
+// round_up(24 * ceil(n / 32), 16) bytes of e2m3 codes, zero from element n on]
+// + scales [ceil(n / 32) E8M0 bytes].  Every output byte is written.
+int hsg_mxfp6_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out,
+                       void* scales, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  const int64_t payload = (24 * ((n + 31) / 32) + 15) / 16 * 16;
+  const int grid = grid_for(n, kFp6Step, 256 * 16);
+  const int rc = for_dtype<false>(src_dtype, [&](auto dt) {
+    return launch(hs_mxfp6_quant<decltype(dt)::value>, grid, stream, src, n, payload, out, scales);
+  });
+  return rc == kNoKernel ? unsupported_dtype("mxfp6 source", src_dtype) : rc;
+}
+
+int hsg_mxfp6_dequantize(int dev, const void* q, const void* scales, int64_t n, void* dst,
+                         int dst_dtype, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  const int grid = grid_for(n, kFp6Step, 256 * 16);
+  const int rc = for_dtype<true>(dst_dtype, [&](auto dt) {
+    return launch(hs_mxfp6_dequant<decltype(dt)::value>, grid, stream, q, scales, n, dst);
+  });
+  return rc == kNoKernel ? unsupported_dtype("mxfp6 dest", dst_dtype) : rc;
 }
 
 // Hadamard-rotated MXFP4: src (bf16/f16/f32, contiguous, n elements) -> out

@@ -267,6 +267,9 @@ HSGPU_ABI = {
                                             c_void_p]),
     "hsg_mxfp4_hadamard_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                               c_void_p]),
+    "hsg_mxfp6_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "hsg_mxfp6_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                     c_void_p]),
     "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
                                    c_int, c_int, c_int, c_int, P(c_int)]),
     "hsg_drain_wait": (c_int, [c_void_p, P(c_uint64), P(c_uint64), c_char_p, P(c_double)]),
@@ -892,6 +895,43 @@ def mxfp4_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch
     assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
     _check(lib.hsg_mxfp4_dequantize(dev, q.data_ptr(), scales.data_ptr(), n, dst.data_ptr(),
                                     dtype_code(dst.dtype), stream_handle), "hsg_mxfp4_dequantize")
+
+
+def mxfp6_payload_bytes(n: int) -> int:
+    return (24 * ((n + 31) // 32) + 15) // 16 * 16
+
+
+def mxfp6_chunk_elems(dtype: torch.dtype) -> int:
+    """Elements one wave of hs_mxfp6_quant / hs_mxfp6_dequant takes per step:
+    a block of 32 per lane, whatever the element size (csrc/hsquant.hip
+    kFp6Step)."""
+    return 64 * 32
+
+
+def mxfp6_quantize(dev: int, src: torch.Tensor, out: torch.Tensor, scales: torch.Tensor,
+                   stream_handle: int) -> None:
+    """MXFP6 (e2m3 codes + E8M0 scale per 32 elements, hs_mxfp6_quant): ``out``
+    gets round_up(24 * ceil(n / 32), 16) bytes (element j of block b in bits
+    [6 j, 6 j + 6) of bytes [24 b, 24 b + 24), zero from element n on),
+    ``scales`` ceil(n / 32)."""
+    lib = require_gpu_lib()
+    n = src.numel()
+    assert src.is_contiguous() and dtype_code(src.dtype) in (10, 11, 12)
+    assert out.numel() >= mxfp6_payload_bytes(n) and scales.numel() >= (n + 31) // 32
+    assert out.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _check(lib.hsg_mxfp6_quantize(dev, src.data_ptr(), dtype_code(src.dtype), n, out.data_ptr(),
+                                  scales.data_ptr(), stream_handle), "hsg_mxfp6_quantize")
+
+
+def mxfp6_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch.Tensor,
+                     stream_handle: int) -> None:
+    lib = require_gpu_lib()
+    n = dst.numel()
+    assert dst.is_contiguous() and dtype_code(dst.dtype) in (10, 11, 12, 13)
+    assert q.numel() >= 24 * ((n + 31) // 32) and scales.numel() >= (n + 31) // 32
+    assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _check(lib.hsg_mxfp6_dequantize(dev, q.data_ptr(), scales.data_ptr(), n, dst.data_ptr(),
+                                    dtype_code(dst.dtype), stream_handle), "hsg_mxfp6_dequantize")
 
 
 def mxfp4_hadamard_tiles(dtype: torch.dtype, restore: bool = False) -> int:

@@ -1,6 +1,7 @@
 """fp8 quantize / dequantize kernels alone on 512 Mi elements (1 GiB of bf16;
 for rocprofv3 --stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128,
-MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32), Hadamard-rotated MXFP4.
+MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32), Hadamard-rotated MXFP4,
+MXFP6 (e2m3 codes, E8M0 per 32).
 Prints one JSON line per
 kernel with host-timed GB/s of HBM traffic (read + written bytes), the time
 between device events around the call, and GB/s of the tensor alone (source
@@ -8,8 +9,8 @@ bytes of a quantize, destination bytes of a dequantize).
 
     fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [mode ...]
 
-Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``, ``mxfp4_hadamard32``.
-``--rounds R`` goes
+Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``, ``mxfp4_hadamard32``,
+``mxfp6``.  ``--rounds R`` goes
 through the list of modes R times, so that two modes alternate and the spread
 of one mode's repeats is seen beside the difference between the two.
 
@@ -64,7 +65,7 @@ def main():
     for mode in modes:
         if mode == "mx_e8m0":
             info = quant.fp8_entry_quant_info(w, rotation="none")
-        elif mode in ("mxfp4", "mxfp4_hadamard32"):
+        elif mode in ("mxfp4", "mxfp4_hadamard32", "mxfp6"):
             os.environ["HIPSNAPSHOT_FP8_FORMAT"] = mode
             info = quant.fp8_entry_quant_info(w, rotation=None if "hadamard" in mode else "none")
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
@@ -74,7 +75,7 @@ def main():
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         blob = torch.zeros(info["total_bytes"], dtype=torch.uint8, device="cuda:0")
         p = info["payload_bytes"]
-        e8m0 = mode in ("mx_e8m0", "mxfp4", "mxfp4_hadamard32")
+        e8m0 = mode in ("mx_e8m0", "mxfp4", "mxfp4_hadamard32", "mxfp6")
         sc = blob[p:] if e8m0 else blob[p:].view(torch.float32)
         back = torch.empty(nw + off, dtype=dtype, device="cuda:0")[off:]
         if mode == "mx_e8m0":
@@ -83,6 +84,9 @@ def main():
         elif mode == "mxfp4":
             q = lambda: native.mxfp4_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mxfp4_dequantize(dev, blob[:p], sc, back, hs)  # noqa: E731
+        elif mode == "mxfp6":
+            q = lambda: native.mxfp6_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
+            dq = lambda: native.mxfp6_dequantize(dev, blob[:p], sc, back, hs)  # noqa: E731
         elif mode == "mxfp4_hadamard32":
             q = lambda: native.mxfp4_hadamard_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mxfp4_hadamard_dequantize(dev, blob[:p], sc, back, hs)  # noqa
