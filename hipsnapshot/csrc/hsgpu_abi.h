@@ -107,6 +107,10 @@ int hsg_mxfp6_quantize(int dev, const void* src, int src_dtype, int64_t n, void*
                        void* scales, void* stream);
 int hsg_mxfp6_dequantize(int dev, const void* q, const void* scales, int64_t n, void* dst,
                          int dst_dtype, void* stream);
+int hsg_nvfp4_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out,
+                       void* scales, void* amax, void* stream);
+int hsg_nvfp4_dequantize(int dev, const void* q, const void* scales, const void* amax, int64_t n,
+                         void* dst, int dst_dtype, void* stream);
 
 // hsgpu.hip: managed memory, stream gate
 int hsg_is_managed(const void* p);

@@ -2,9 +2,11 @@
 // blockwise OCP-fp8 (e4m3fn) with an f32 scale per block, MX fp8 (one E8M0
 // scale byte per 32 elements), Hadamard-rotated fp8 on the matrix cores and
 // MXFP4 (e2m1 nibbles, one E8M0 scale byte per 32 elements, gfx950's scaled
-// fp4 conversions) and MXFP6 (e2m3 codes, 32 in 24 bytes, the same scale, a
-// whole block per conversion) -- and their hsg_*quantize / hsg_*dequantize
-// entry points.
+// fp4 conversions), MXFP6 (e2m3 codes, 32 in 24 bytes, the same scale, a
+// whole block per conversion) and two-level-scaled FP4 (e2m1 nibbles, one
+// e4m3fn scale byte per 16 elements under one f32 scale for the tensor, found
+// by a reduction pass of its own) -- and their hsg_*quantize /
+// hsg_*dequantize entry points.
 // Wave size is 64.
 
 #include <algorithm>
@@ -461,9 +463,10 @@ __device__ __forceinline__ uint32_t fp4_sign(const mx_u32x4& w, int j) {
   else return (w[j >> 1] >> (16 * (j & 1) + 15)) & 1u;
 }
 
-// largest finite |x| pattern of a lane's 16 B, kFp4NanKey if one is a NaN;
-// `nonfinite`: the piece holds an inf or a NaN
-template <int DT>
+// largest finite |x| pattern of a lane's 16 B, kFp4NanKey if one is a NaN
+// (kKeyNan; without it a NaN is left out like an inf); `nonfinite`: the piece
+// holds an inf or a NaN
+template <int DT, bool kKeyNan = true>
 __device__ __forceinline__ uint32_t fp4_lane_key(const mx_u32x4& w, bool& nonfinite) {
   constexpr uint32_t kInf = kInfBits<DT>;
   uint32_t a;
@@ -483,7 +486,7 @@ __device__ __forceinline__ uint32_t fp4_lane_key(const mx_u32x4& w, bool& nonfin
 #pragma unroll
     for (int j = 0; j < (DT == kF32 ? 4 : 8); ++j) {
       const uint32_t p = fp4_abs_bits<DT>(w, j);
-      a = p > kInf ? kFp4NanKey : (p < kInf ? max(a, p) : a);
+      a = (kKeyNan && p > kInf) ? kFp4NanKey : (p < kInf ? max(a, p) : a);
     }
   }
   return a;
@@ -544,6 +547,71 @@ __device__ __forceinline__ uint32_t fp4_pack(const mx_u32x4& w, uint32_t sb, boo
   return r;
 }
 
+// A chunk's nibbles and scale bytes to memory, for blocks of BLK elements (32:
+// MXFP4, 16: the two-level format below): `code[u]` holds the lane's EPL
+// nibbles of load u, byte u of `sbytes` the scale byte of its block.  `full`:
+// the 4-B stores described above; otherwise byte by byte, zeros from element
+// n up to `payload`, and the lane of the last scale byte also zeroes
+// scales[nblocks .. scale_end).
+template <int EPL, int BLK>
+__device__ __forceinline__ void fp4_store_chunk(const uint32_t* code, uint32_t sbytes,
+                                                int64_t base, int lane, bool full, int64_t n,
+                                                int64_t payload, int64_t scale_end,
+                                                uint8_t* __restrict__ out,
+                                                uint8_t* __restrict__ scales) {
+  constexpr int LPB = BLK / EPL;  // lanes per block
+  constexpr int BPL = 64 / LPB;   // blocks (scale bytes) per wave load
+  constexpr int U = kStreamU;
+  if (full) {
+    if constexpr (EPL == 8) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+        __builtin_nontemporal_store(code[u], reinterpret_cast<uint32_t*>(out + (e0 >> 1)));
+      }
+    } else {
+      const bool odd = lane & 1;
+#pragma unroll
+      for (int u = 0; u < U; u += 2) {
+        // even lane: (own, lane + 1) half-words of load u; odd lane:
+        // (lane - 1, own) of load u + 1
+        const uint32_t other = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(
+            static_cast<int>(odd ? code[u] : code[u + 1]), 0xB1, 0xF, 0xF, false));  // lane ^ 1
+        const uint32_t word = odd ? ((other & 0xffffu) | (code[u + 1] << 16))
+                                  : ((code[u] & 0xffffu) | (other << 16));
+        const int64_t e0 = base + (int64_t(u + odd) * 64 + (lane & ~1)) * EPL;
+        __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(out + (e0 >> 1)));
+      }
+    }
+    // scale byte s of the chunk is byte s / BPL of `sbytes` in lane
+    // (s % BPL) * LPB; lane l < U * BPL / 4 stores bytes 4 l .. 4 l + 3
+    const int s = (4 * lane) % (U * BPL);
+    const int l0 = (s % BPL) * LPB;
+    uint32_t word = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      word |= ((uint32_t(__shfl(int(sbytes), l0 + j * LPB, 64)) >> (8 * (s / BPL))) & 0xffu)
+              << (8 * j);
+    if (lane < U * BPL / 4)
+      __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(scales + base / BLK) + lane);
+  } else {
+    const int64_t nblocks = (n + BLK - 1) / BLK;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      if ((lane % LPB) == 0 && e0 < n) {
+        scales[e0 / BLK] = static_cast<uint8_t>(sbytes >> (8 * u));
+        if (e0 / BLK == nblocks - 1)
+          for (int64_t at = nblocks; at < scale_end; ++at) scales[at] = 0;
+      }
+      for (int b = 0; b < EPL / 2; ++b) {
+        const int64_t at = (e0 >> 1) + b;
+        if (at < payload) out[at] = 2 * at < n ? static_cast<uint8_t>(code[u] >> (8 * b)) : 0;
+      }
+    }
+  }
+}
+
 // `out` holds `payload` >= ceil(n / 2) bytes, `scales` ceil(n / 32)
 template <int DT>
 __global__ void __launch_bounds__(kBlock)
@@ -552,7 +620,6 @@ hs_mxfp4_quant(const char* __restrict__ src, int64_t n, int64_t payload,
   constexpr int ES = (DT == kF32) ? 4 : 2;
   constexpr int EPL = 16 / ES;   // elements per lane per load
   constexpr int LPB = 32 / EPL;  // lanes per block
-  constexpr int BPL = 64 / LPB;  // blocks (scale bytes) per wave load
   constexpr int U = kStreamU;
   static_assert(U == 4, "a lane packs its U scale bytes into one word");
   constexpr int64_t kChunk = 64LL * EPL * U;
@@ -586,49 +653,8 @@ hs_mxfp4_quant(const char* __restrict__ src, int64_t n, int64_t payload,
       sbytes |= sb << (8 * u);
       code[u] = fp4_pack<DT>(raw[u], sb, nonfinite);
     }
-    if (full) {
-      if constexpr (EPL == 8) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
-          __builtin_nontemporal_store(code[u], reinterpret_cast<uint32_t*>(out + (e0 >> 1)));
-        }
-      } else {
-        const bool odd = lane & 1;
-#pragma unroll
-        for (int u = 0; u < U; u += 2) {
-          // even lane: (own, lane + 1) half-words of load u; odd lane:
-          // (lane - 1, own) of load u + 1
-          const uint32_t other = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(
-              static_cast<int>(odd ? code[u] : code[u + 1]), 0xB1, 0xF, 0xF, false));  // lane ^ 1
-          const uint32_t word = odd ? ((other & 0xffffu) | (code[u + 1] << 16))
-                                    : ((code[u] & 0xffffu) | (other << 16));
-          const int64_t e0 = base + (int64_t(u + odd) * 64 + (lane & ~1)) * EPL;
-          __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(out + (e0 >> 1)));
-        }
-      }
-      // scale byte s of the chunk is byte s / BPL of `sbytes` in lane
-      // (s % BPL) * LPB; lane l < U * BPL / 4 stores bytes 4 l .. 4 l + 3
-      const int s = (4 * lane) % (U * BPL);
-      const int l0 = (s % BPL) * LPB;
-      uint32_t word = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        word |= ((uint32_t(__shfl(int(sbytes), l0 + j * LPB, 64)) >> (8 * (s / BPL))) & 0xffu)
-                << (8 * j);
-      if (lane < U * BPL / 4)
-        __builtin_nontemporal_store(word, reinterpret_cast<uint32_t*>(scales + base / 32) + lane);
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
-        if ((lane % LPB) == 0 && e0 < n) scales[e0 / 32] = static_cast<uint8_t>(sbytes >> (8 * u));
-        for (int b = 0; b < EPL / 2; ++b) {
-          const int64_t at = (e0 >> 1) + b;
-          if (at < payload) out[at] = 2 * at < n ? static_cast<uint8_t>(code[u] >> (8 * b)) : 0;
-        }
-      }
-    }
+    fp4_store_chunk<EPL, 32>(code, sbytes, base, lane, full, n, payload, (n + 31) / 32, out,
+                             scales);
   }
 }
 
@@ -701,6 +727,281 @@ hs_mxfp4_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scal
 #pragma unroll
       for (int j = 0; j < EPL; ++j)
         f[j] = sc[u] == kE8m0Nan ? __builtin_nanf("") : ldexpf(p[j >> 1][j & 1], k);
+      if (full) {
+        fp4_store16<DT>(dst + e0 * DES, f);
+      } else {
+        for (int j = 0; j < EPL && e0 + j < n; ++j) store_from_f32(dst + (e0 + j) * DES, DT, f[j]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Two-level-scaled FP4 (format "fp4_e2m1_nv", the "NVFP4" layout): MXFP4's e2m1
+// nibbles in MXFP4's order, one e4m3fn scale byte s8 per 16 elements and one
+// fp32 A, the tensor's amax over its finite elements, behind the scale bytes
+// (zero-padded to a multiple of 4).  Every step of the rule is one fp32
+// operation, so ops/quant.py nvfp4_quantize_reference gives the same bytes:
+//   * ts = max(A / 2688, 2^-117) (2688 = 448 * 6; quantizer and restore
+//     evaluate the same expression; the floor keeps d >= 2^-126 below);
+//   * s8 = e4m3fn_rne(min(bamax / (6 * ts), 448)), bamax the block's amax over
+//     its finite elements; d = f32(s8) * ts;
+//   * code = e2m1_rne(clamp(x * (1 / d), -6, 6)), ties to the even index, the
+//     source's sign kept on zero; the clamp is part of the rule (s8 is rounded
+//     to nearest, so bamax / d can exceed 6) and turns +-inf into +-6;
+//   * s8 == 0 (bamax is 0 or more than about 2^22 below A): 1 / d is inf, so
+//     every code of the block is its element's sign bit alone;
+//   * a block that holds a NaN stores the e4m3fn NaN 0x7F and 8 zero bytes and
+//     restores as positive quiet NaNs; a NaN takes no part in A;
+//   * restore is q * d, one fp32 product, then the one rounding to the
+//     destination (pack16 / store_from_f32).
+// payload = round_up(ceil(n / 2), 16) bytes, zero from element n on.
+//
+// Three kernels on one stream; a small one clears the A slot first.
+// hs_nvfp4_amax, the project's one tensor-wide reduction: a grid-stride stream
+// of wave-contiguous 16-B loads, 8 in flight, fp4_lane_key without the NaN key
+// per piece (unsigned max of |x| patterns, which orders finite values), a
+// 6-step xor-shuffle at the end of the wave's stride and at most one vector
+// atomic max per workgroup on the slot -- the f32 pattern, to which a 16-bit
+// key is widened first.  A max does not depend on the order of the atomics.  The
+// loads are plain ones: hs_nvfp4_quant reads the same bytes again.
+// hs_nvfp4_quant has hs_mxfp4_quant's shape and stores (fp4_store_chunk): a
+// block is 2 lanes (bf16 / f16) or 4 (f32), so its key needs one or two DPP
+// quad moves, and a chunk carries 128 or 64 scale bytes.  Every lane forms ts
+// from A, then per load the two correctly rounded divisions of its block
+// (bamax / (6 ts) and 1 / d); s8 comes from v_cvt_pk_fp8_f32 and goes back
+// through v_cvt_f32_fp8.  The 16-bit scaled fp4 conversions read only an
+// exponent field, so every source is unpacked to f32, multiplied by 1 / d,
+// clamped by v_med3_f32 and converted by v_cvt_scalef32_pk_fp4_f32 at scale 1.
+// The clamp makes +-6 of an inf before the conversion sees it; patched are the
+// NaN block and the s8 == 0 block (inf * inf and 0 * inf are not what the rule
+// says).
+// hs_nvfp4_dequant is hs_mxfp4_dequant with d = f32(s8) * ts per lane (16 is a
+// multiple of the 8 / 4 / 2 elements of a lane) and one v_mul_f32 per element.
+// These kernels are compiled without the packed f32 instructions
+// (HS_NO_PK_F32): their per-element products are plain v_mul_f32.
+// ---------------------------------------------------------------------------
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HS_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HS_NO_PK_F32
+#endif
+
+constexpr float kNvfp4Top = 2688.0f;       // 448 * 6
+constexpr float kNvfp4MinTs = 0x1p-117f;   // ts * 2^-9 (the smallest s8) >= 2^-126
+constexpr uint32_t kE4m3Nan = 0x7fu;
+
+__device__ __forceinline__ float nvfp4_tensor_scale(float amax) {
+  return fmaxf(amax / kNvfp4Top, kNvfp4MinTs);
+}
+
+// the f32 value of a finite |x| pattern of the source dtype
+template <int DT>
+__device__ __forceinline__ float fp4_key_value(uint32_t key) {
+  if constexpr (DT == kF32) return __uint_as_float(key);
+  else return mx_unpack<DT>(key, 0);
+}
+
+__global__ void hs_nvfp4_clear(uint32_t* __restrict__ amax) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *amax = 0;
+}
+
+constexpr int kAmaxU = 8;           // 16-B loads in flight per lane of hs_nvfp4_amax
+constexpr int kAmaxGrid = 256 * 4;  // its workgroups at most
+
+template <int DT>
+__global__ void HS_NO_PK_F32 __launch_bounds__(kBlock)
+hs_nvfp4_amax(const char* __restrict__ src, int64_t n, uint32_t* __restrict__ amax) {
+  constexpr int ES = (DT == kF32) ? 4 : 2;
+  constexpr int EPL = 16 / ES;
+  constexpr int U = kAmaxU;
+  __shared__ uint32_t wave_key[kBlock / 64];
+  constexpr int64_t kChunk = 64LL * EPL * U;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+  uint32_t key = 0;
+  for (int64_t base = wave0 * kChunk; base < n; base += nwaves * kChunk) {
+    const bool full = aligned && base + kChunk <= n;
+    mx_u32x4 raw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      raw[u] = full ? *reinterpret_cast<const mx_u32x4*>(src + e0 * ES)
+                    : load16_elems<ES>(src, e0, n);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bool nonfinite;
+      key = max(key, fp4_lane_key<DT, false>(raw[u], nonfinite));
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) key = max(key, uint32_t(__shfl_xor(int(key), o, 64)));
+  // Atomics on one address complete one after the other, about 12 ns each on
+  // an MI355X: 16384 waves, each with its atomic, took 0.2 ms whatever the
+  // tensor's size (waves that end together all read an empty slot, so a test
+  // before the atomic alone did not help).  So a workgroup joins its waves'
+  // keys in LDS and issues one atomic, the grid is kAmaxGrid workgroups at
+  // most with kAmaxU loads in flight per lane to make up for the fewer waves,
+  // and the atomic is left out if the slot already holds as much (a stale read
+  // only costs a needless atomic).
+  if (lane == 0) wave_key[threadIdx.x >> 6] = key;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < kBlock / 64; ++i) key = max(key, wave_key[i]);
+    const uint32_t bits = __float_as_uint(fp4_key_value<DT>(key));
+    if (bits > __hip_atomic_load(amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMax(amax, bits);
+  }
+}
+
+// s8 of a block from its key (finite pattern or kFp4NanKey), and 1 / d for its
+// elements: inf when s8 == 0
+template <int DT>
+__device__ __forceinline__ uint32_t nvfp4_block_scale(uint32_t key, float ts, float six_ts,
+                                                      float& inv) {
+  const float quot = fminf(fp4_key_value<DT>(key) / six_ts, kFp8Max);
+  const int word = __builtin_amdgcn_cvt_pk_fp8_f32(quot, 0.f, 0, false);
+  inv = 1.f / (__builtin_amdgcn_cvt_f32_fp8(word, 0) * ts);
+  return key == kFp4NanKey ? kE4m3Nan : (static_cast<uint32_t>(word) & 0xffu);
+}
+
+// codes of a lane's 16 B under scale byte `s8`, `inv` = 1 / d: 8 nibbles
+// (bf16 / f16) or 4 (f32, low half-word), element j in nibble j
+template <int DT>
+__device__ __forceinline__ uint32_t nvfp4_pack(const mx_u32x4& w, uint32_t s8, float inv) {
+  if (s8 == kE4m3Nan) return 0;
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+  if (s8 == 0) {  // the sign bits alone: bit 3 of each nibble
+    if constexpr (DT == kF32) {
+      return ((w0 >> 31) << 3) | ((w1 >> 31) << 7) | ((w2 >> 31) << 11) | ((w3 >> 31) << 15);
+    } else {
+      const uint32_t ws[4] = {w0, w1, w2, w3};
+      uint32_t r = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        r |= (((ws[i] >> 15) & 1u) << (8 * i + 3)) | ((ws[i] >> 31) << (8 * i + 7));
+      return r;
+    }
+  }
+  constexpr int EPL = (DT == kF32) ? 4 : 8;
+  float v[EPL];
+  unpack16<DT>(w, v);
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) v[j] = __builtin_amdgcn_fmed3f(v[j] * inv, -6.f, 6.f);
+  uint32_t r = 0;
+  r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, v[0], v[1], 1.0f, 0);
+  r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, v[2], v[3], 1.0f, 1);
+  if constexpr (EPL == 8) {
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, v[4], v[5], 1.0f, 2);
+    r = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(r, v[6], v[7], 1.0f, 3);
+  }
+  return r;
+}
+
+// `out` holds `payload` >= ceil(n / 2) bytes, `scales` round_up(ceil(n / 16), 4)
+template <int DT>
+__global__ void HS_NO_PK_F32 __launch_bounds__(kBlock)
+hs_nvfp4_quant(const char* __restrict__ src, int64_t n, int64_t payload,
+               uint8_t* __restrict__ out, uint8_t* __restrict__ scales,
+               const float* __restrict__ amax) {
+  constexpr int ES = (DT == kF32) ? 4 : 2;
+  constexpr int EPL = 16 / ES;   // elements per lane per load
+  constexpr int LPB = 16 / EPL;  // lanes per block: 2 or 4, inside a quad
+  constexpr int U = kStreamU;
+  static_assert(U == 4, "a lane packs its U scale bytes into one word");
+  constexpr int64_t kChunk = 64LL * EPL * U;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(out) & 3) == 0 &&
+                       (reinterpret_cast<uintptr_t>(scales) & 3) == 0;
+  const float ts = nvfp4_tensor_scale(*amax);
+  const float six_ts = 6.f * ts;
+  const int64_t scale_end = ((n + 15) / 16 + 3) / 4 * 4;
+  for (int64_t base = wave0 * kChunk; base < n; base += nwaves * kChunk) {
+    const bool full = aligned && base + kChunk <= n;
+    mx_u32x4 raw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      raw[u] = full ? __builtin_nontemporal_load(reinterpret_cast<const mx_u32x4*>(src + e0 * ES))
+                    : load16_elems<ES>(src, e0, n);
+    }
+    uint32_t code[U];
+    uint32_t sbytes = 0;  // byte u: the scale of this lane's block of load u
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      bool nonfinite;
+      uint32_t key = fp4_lane_key<DT>(raw[u], nonfinite);
+      key = max(key, uint32_t(__builtin_amdgcn_mov_dpp(int(key), 0xB1, 0xF, 0xF, false)));  // ^ 1
+      if constexpr (LPB == 4)
+        key = max(key, uint32_t(__builtin_amdgcn_mov_dpp(int(key), 0x4E, 0xF, 0xF, false)));  // ^ 2
+      float inv;
+      const uint32_t s8 = nvfp4_block_scale<DT>(key, ts, six_ts, inv);
+      sbytes |= s8 << (8 * u);
+      code[u] = nvfp4_pack<DT>(raw[u], s8, inv);
+    }
+    fp4_store_chunk<EPL, 16>(code, sbytes, base, lane, full, n, payload, scale_end, out, scales);
+  }
+}
+
+template <int DT>
+__global__ void HS_NO_PK_F32 __launch_bounds__(kBlock)
+hs_nvfp4_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scales,
+                 const float* __restrict__ amax, int64_t n, char* __restrict__ dst) {
+  constexpr int DES = (DT == kF32) ? 4 : (DT == kF64 ? 8 : 2);
+  constexpr int EPL = 16 / DES;  // elements per lane per step = one 16-B store
+  constexpr int QB = EPL / 2;    // payload bytes per lane per step
+  static_assert(16 % EPL == 0, "one scale per lane");
+  constexpr int U = kStreamU;
+  constexpr int64_t kChunk = 64LL * EPL * U;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) +
+                        __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(q) & (QB - 1)) == 0 &&
+                       (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  const float ts = nvfp4_tensor_scale(*amax);
+  for (int64_t base = wave0 * kChunk; base < n; base += nwaves * kChunk) {
+    const bool full = aligned && base + kChunk <= n;
+    uint32_t raw[U];
+    uint32_t sc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      if (full) {
+        if constexpr (QB == 4) raw[u] = *reinterpret_cast<const uint32_t*>(q + (e0 >> 1));
+        else if constexpr (QB == 2) raw[u] = *reinterpret_cast<const uint16_t*>(q + (e0 >> 1));
+        else raw[u] = q[e0 >> 1];
+      } else {
+        raw[u] = 0;
+        for (int b = 0; b < QB && e0 + 2 * b < n; ++b) raw[u] |= uint32_t(q[(e0 >> 1) + b]) << (8 * b);
+      }
+      sc[u] = e0 < n ? scales[e0 / 16] : 0u;  // past n: nothing stored
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      mx_f32x2 p[4];  // the byte select must be an immediate
+      p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 0);
+      if constexpr (QB >= 2) p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 1);
+      if constexpr (QB == 4) {
+        p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 2);
+        p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 3);
+      }
+      const bool nan = (sc[u] & 0x7fu) == kE4m3Nan;  // the byte of a NaN block
+      const float d = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(sc[u]), 0) * ts;
+      float f[EPL];
+#pragma unroll
+      for (int j = 0; j < EPL; ++j) f[j] = nan ? __builtin_nanf("") : p[j >> 1][j & 1] * d;
       if (full) {
         fp4_store16<DT>(dst + e0 * DES, f);
       } else {
@@ -1702,6 +2003,11 @@ int unsupported_dtype(const char* what, int dt) {
   return -1002;
 }
 
+int misaligned_amax(const void* amax) {
+  hs_set_error("nvfp4 amax slot %p is not 4-byte aligned", amax);
+  return -1003;
+}
+
 template <class... P, class... A>
 int launch(void (*kernel)(P...), int grid, void* stream, A... args) {
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
@@ -1829,6 +2135,43 @@ int hsg_mxfp4_dequantize(int dev, const void* q, const void* scales, int64_t n, 
     return launch(hs_mxfp4_dequant<decltype(dt)::value>, grid, stream, q, scales, n, dst);
   });
   return rc == kNoKernel ? unsupported_dtype("mxfp4 dest", dst_dtype) : rc;
+}
+
+// Two-level-scaled FP4: src (bf16/f16/f32, contiguous, n elements) -> out
+// [payload = round_up(ceil(n / 2), 16) bytes of e2m1 nibbles, zero from element
+// n on] + scales [ceil(n / 16) e4m3fn bytes, zero-padded to a multiple of 4] +
+// amax [one f32, 4-byte aligned: the amax over the finite elements].  Every
+// output byte is written.  Three launches on `stream`: clear, amax, quantize.
+int hsg_nvfp4_quantize(int dev, const void* src, int src_dtype, int64_t n, void* out,
+                       void* scales, void* amax, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  if (reinterpret_cast<uintptr_t>(amax) & 3) return misaligned_amax(amax);
+  const int64_t payload = ((n + 1) / 2 + 15) / 16 * 16;
+  const int grid = grid_for(n, stream_chunk(src_dtype), 256 * 16);
+  const int rc = for_dtype<false>(src_dtype, [&](auto dt) {
+    constexpr int kDt = decltype(dt)::value;
+    int r = launch(hs_nvfp4_clear, 1, stream, amax);
+    if (r == 0)
+      r = launch(hs_nvfp4_amax<kDt>,
+                 grid_for(n, stream_chunk(src_dtype) / kStreamU * kAmaxU, kAmaxGrid), stream, src,
+                 n, amax);
+    if (r == 0) r = launch(hs_nvfp4_quant<kDt>, grid, stream, src, n, payload, out, scales, amax);
+    return r;
+  });
+  return rc == kNoKernel ? unsupported_dtype("nvfp4 source", src_dtype) : rc;
+}
+
+int hsg_nvfp4_dequantize(int dev, const void* q, const void* scales, const void* amax, int64_t n,
+                         void* dst, int dst_dtype, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (n <= 0) return 0;
+  if (reinterpret_cast<uintptr_t>(amax) & 3) return misaligned_amax(amax);
+  const int grid = grid_for(n, stream_chunk(dst_dtype), 256 * 16);
+  const int rc = for_dtype<true>(dst_dtype, [&](auto dt) {
+    return launch(hs_nvfp4_dequant<decltype(dt)::value>, grid, stream, q, scales, amax, n, dst);
+  });
+  return rc == kNoKernel ? unsupported_dtype("nvfp4 dest", dst_dtype) : rc;
 }
 
 // MXFP6: src (bf16/f16/f32, contiguous, n elements) -> out [payload =

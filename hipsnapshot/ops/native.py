@@ -270,6 +270,10 @@ HSGPU_ABI = {
     "hsg_mxfp6_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "hsg_mxfp6_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                      c_void_p]),
+    "hsg_nvfp4_quantize": (c_int, [c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "hsg_nvfp4_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                     c_void_p]),
     "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
                                    c_int, c_int, c_int, c_int, P(c_int)]),
     "hsg_drain_wait": (c_int, [c_void_p, P(c_uint64), P(c_uint64), c_char_p, P(c_double)]),
@@ -932,6 +936,53 @@ def mxfp6_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, dst: torch
     assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
     _check(lib.hsg_mxfp6_dequantize(dev, q.data_ptr(), scales.data_ptr(), n, dst.data_ptr(),
                                     dtype_code(dst.dtype), stream_handle), "hsg_mxfp6_dequantize")
+
+
+def nvfp4_scale_bytes(n: int) -> int:
+    """One e4m3fn byte per 16 elements, zero-padded to a multiple of 4."""
+    return ((n + 15) // 16 + 3) // 4 * 4
+
+
+def nvfp4_chunk_elems(dtype: torch.dtype) -> int:
+    """Elements one wave of hs_nvfp4_quant / hs_nvfp4_dequant takes per step:
+    64 lanes x 16 B x 4 in flight (csrc/hsquant.hip kStreamU); hs_nvfp4_amax
+    takes twice as many (kAmaxU)."""
+    return 64 * 4 * (16 // torch.empty(0, dtype=dtype).element_size())
+
+
+def _nvfp4_amax_slot(amax: torch.Tensor) -> None:
+    assert amax.numel() * amax.element_size() >= 4 and amax.data_ptr() % 4 == 0
+    assert amax.dtype in (torch.uint8, torch.float32)
+
+
+def nvfp4_quantize(dev: int, src: torch.Tensor, out: torch.Tensor, scales: torch.Tensor,
+                   amax: torch.Tensor, stream_handle: int) -> None:
+    """Two-level-scaled FP4 (hs_nvfp4_amax, then hs_nvfp4_quant): ``out`` gets
+    round_up(ceil(n / 2), 16) bytes of e2m1 nibbles in the ``mxfp4`` order,
+    ``scales`` ceil(n / 16) e4m3fn bytes and the zero pad to a multiple of 4,
+    ``amax`` (4 bytes, 4-byte aligned) the fp32 amax over the finite elements."""
+    lib = require_gpu_lib()
+    n = src.numel()
+    assert src.is_contiguous() and dtype_code(src.dtype) in (10, 11, 12)
+    assert out.numel() >= mxfp4_payload_bytes(n) and scales.numel() >= nvfp4_scale_bytes(n)
+    assert out.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _nvfp4_amax_slot(amax)
+    _check(lib.hsg_nvfp4_quantize(dev, src.data_ptr(), dtype_code(src.dtype), n, out.data_ptr(),
+                                  scales.data_ptr(), amax.data_ptr(), stream_handle),
+           "hsg_nvfp4_quantize")
+
+
+def nvfp4_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, amax: torch.Tensor,
+                     dst: torch.Tensor, stream_handle: int) -> None:
+    lib = require_gpu_lib()
+    n = dst.numel()
+    assert dst.is_contiguous() and dtype_code(dst.dtype) in (10, 11, 12, 13)
+    assert q.numel() >= (n + 1) // 2 and scales.numel() >= (n + 15) // 16
+    assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
+    _nvfp4_amax_slot(amax)
+    _check(lib.hsg_nvfp4_dequantize(dev, q.data_ptr(), scales.data_ptr(), amax.data_ptr(), n,
+                                    dst.data_ptr(), dtype_code(dst.dtype), stream_handle),
+           "hsg_nvfp4_dequantize")
 
 
 def mxfp4_hadamard_tiles(dtype: torch.dtype, restore: bool = False) -> int:

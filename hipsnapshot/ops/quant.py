@@ -194,6 +194,59 @@ Measured relative L2 error of the CPU references on 2^20 seeded values,
 0.1011; Student-t(3) 0.1505 / 0.1129; Student-t(5) 0.1327 / 0.1151; Laplace
 0.1322 / 0.1151; N(0, 1) with every 257th value x50: 0.1361 / 0.1050.  About a
 quarter lower on heavy tails, 2.6 % higher on pure Gaussians.
+
+Two-level-scaled FP4 layout (opt-in, ``HIPSNAPSHOT_FP8_FORMAT=nvfp4``): the
+"NVFP4" layout that other tools read, 4.5 bits per element::
+
+    {"format": "fp4_e2m1_nv", "block": 16, "scale": "e4m3+fp32", "rotation": "none",
+     "orig_dtype": ..., "nblocks": B = ceil(n / 16),
+     "payload_bytes": P = round_up(ceil(n / 2), 16),
+     "total_bytes": P + round_up(B, 4) + 4}
+
+blob = ``[P payload bytes][B e4m3fn scale bytes][zero pad to 4][fp32 A]``.  The
+payload is ``mxfp4``'s: the same e2m1 codes, nibble order and zero fill from
+element ``n`` on.  ``A`` is the tensor's amax over its finite elements, 0 when
+it has no finite non-zero element.  An MX scale is a power of two shared by 32
+elements, so a block's largest value lands anywhere in the top octave of the
+grid; here a block of 16 has an e4m3 scale, which puts it within 1/16 of 6, and
+``A`` places the e4m3 range.  Every step below is ONE fp32 operation, in
+``hs_nvfp4_amax`` / ``hs_nvfp4_quant`` / ``hs_nvfp4_dequant`` and in the
+references alike:
+
+* tensor scale ``ts = max(A / 2688, 2^-117)`` (2688 = 448 * 6, the quotient
+  correctly rounded), evaluated the same way by the quantizer and the restore.
+  The floor keeps every non-zero block scale ``d >= 2^-126`` so that ``1 / d``
+  is finite (the reason for the floor of the fp32 block scales above);
+* block scale byte ``s8 = e4m3fn_rne(min(bamax / (6 * ts), 448))`` with
+  ``bamax`` the block's amax over its finite elements and ``6 * ts`` an fp32
+  product: one correctly rounded division per block.  Decoded: ``d = f32(s8) *
+  ts``, an fp32 product;
+* element ``y = clamp(x * (1 / d), -6, 6)``, then the e2m1 code, round to
+  nearest with ties to the even index, the source's sign bit kept also on a
+  zero result.  The clamp is part of the rule: ``s8`` is rounded to nearest, so
+  ``bamax / d`` can exceed 6;
+* ``s8 == 0`` (an all-zero block, or one whose amax is more than about 2^22
+  below ``A``): every code of the block is its element's sign bit alone, an inf
+  included, and the block restores as signed zeros.  That is the format's
+  floor: a tensor whose magnitudes span a large range ACROSS blocks -- Adam
+  second moments, whose rows differ by tens of octaves -- loses its small
+  blocks entirely and should stay on ``mx``, whose scale is free per block;
+* ``+-inf`` becomes code ``+-6`` (the clamp) and sets neither ``bamax`` nor
+  ``A``;
+* a block that holds a NaN stores the e4m3fn NaN byte ``0x7F`` and 8 zero
+  payload bytes and restores as 16 positive quiet NaNs (the MXFP4 convention);
+  the NaN takes no part in ``A`` (the block's finite elements do);
+* restore is ``q * d``, one fp32 product, then one rounding to the target
+  dtype.
+
+A CPU take and a GPU take write identical bytes for bf16, f16 and fp32 sources,
+and a restore on either side equals ``nvfp4_dequantize_reference`` bit for bit
+for bf16, f16, fp32 and fp64 targets.
+
+Relative L2 error of a float64 model of the rules on 2^20 seeded values,
+``mxfp4`` / ``mxfp4_hadamard32`` / ``nvfp4``: N(0, 1) 0.1154 / 0.1184 / 0.0950;
+Student-t(2) 0.1327 / 0.1011 / 0.0645; Laplace 0.1321 / 0.1151 / 0.0927: 18 to
+50 % less error than ``mxfp4`` for 6 % more bytes.
 """
 
 from __future__ import annotations
@@ -266,6 +319,18 @@ def mxfp6_payload_bytes(n: int) -> int:
     return _round_up(24 * ((n + MX_BLOCK - 1) // MX_BLOCK), 16)
 
 
+NV_BLOCK = 16
+
+
+def is_nvfp4(info: Dict[str, Any]) -> bool:
+    return info.get("format") == "fp4_e2m1_nv"
+
+
+def nvfp4_payload_bytes(n: int) -> int:
+    """The ``mxfp4`` payload: two codes per byte, rounded up to 16."""
+    return mxfp4_payload_bytes(n)
+
+
 def fp8_supported(t: torch.Tensor) -> bool:
     return t.dtype in FP8_QUANTIZABLE_DTYPES and hasattr(torch, "float8_e4m3fn") \
         and t.numel() > 0
@@ -298,6 +363,12 @@ def fp8_entry_quant_info(t: torch.Tensor, vpt: int = DEFAULT_VPT,
         return {"format": "fp6_e2m3_mx", "block": MX_BLOCK, "scale": "e8m0",
                 "rotation": "none", "orig_dtype": dtype_to_string(t.dtype), "nblocks": nblocks,
                 "payload_bytes": payload, "total_bytes": payload + nblocks}
+    if rotation == "none" and knobs.fp8_format() == "nvfp4":
+        payload = nvfp4_payload_bytes(n)
+        nblocks = (n + NV_BLOCK - 1) // NV_BLOCK
+        return {"format": "fp4_e2m1_nv", "block": NV_BLOCK, "scale": "e4m3+fp32",
+                "rotation": "none", "orig_dtype": dtype_to_string(t.dtype), "nblocks": nblocks,
+                "payload_bytes": payload, "total_bytes": payload + _round_up(nblocks, 4) + 4}
     if rotation == "none" and default_scale() == "e8m0":
         payload = _round_up(n, 16)
         nblocks = (n + MX_BLOCK - 1) // MX_BLOCK
@@ -418,6 +489,14 @@ def mxfp4_exponents(amax: torch.Tensor) -> torch.Tensor:
     return torch.where(ok, k, torch.zeros_like(k)).clamp(-127, 127).to(torch.int32)
 
 
+def _e2m1_index(y: torch.Tensor) -> torch.Tensor:
+    """Index of the nearest ``E2M1_VALUES`` magnitude to ``y >= 0`` (uint8): the
+    comparisons are with the midpoints of the grid; a tie goes to the even
+    index."""
+    return ((y > 0.25).to(torch.uint8) + (y >= 0.75) + (y > 1.25) + (y >= 1.75) + (y > 2.5)
+            + (y >= 3.5) + (y > 5.0))
+
+
 def mxfp4_quantize_reference(x: torch.Tensor):
     """MXFP4 reference: returns (payload[round_up(ceil(n / 2), 16)] uint8 with
     element 2i in the low nibble of byte i and zeros from element n on, scale
@@ -432,10 +511,7 @@ def mxfp4_quantize_reference(x: torch.Tensor):
     amax = torch.where(torch.isfinite(a), a, torch.zeros_like(a)).amax(dim=1)  # finite only
     k = mxfp4_exponents(amax)
     y = a * pow2(-k)[:, None]  # exact, at most 6 (inf stays inf: index 7)
-    # midpoints of the grid; a tie goes to the even index
-    idx = ((y > 0.25).to(torch.uint8) + (y >= 0.75) + (y > 1.25) + (y >= 1.75) + (y > 2.5)
-           + (y >= 3.5) + (y > 5.0))
-    codes = idx | (torch.signbit(blocks).to(torch.uint8) << 3)
+    codes = _e2m1_index(y) | (torch.signbit(blocks).to(torch.uint8) << 3)
     has_nan = torch.isnan(blocks).any(dim=1)
     codes = torch.where(has_nan[:, None], torch.zeros_like(codes), codes).reshape(-1)
     sbytes = torch.where(has_nan, torch.full_like(k, E8M0_NAN), k + 127).to(torch.uint8)
@@ -444,23 +520,88 @@ def mxfp4_quantize_reference(x: torch.Tensor):
     return payload, sbytes
 
 
+def _e2m1_decode(payload: torch.Tensor, n: int, nblocks: int, block: int) -> torch.Tensor:
+    """The fp32 values of the nibbles of elements ``[0, n)`` as ``[nblocks,
+    block]`` (zeros past ``n``)."""
+    p = payload[: (n + 1) // 2]
+    codes = torch.zeros(nblocks * block, dtype=torch.uint8, device=p.device)
+    codes[0: 2 * p.numel(): 2] = p & 0xF
+    codes[1: 2 * p.numel(): 2] = p >> 4
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=p.device)[(codes & 7).long()]
+    return torch.where((codes & 8) != 0, -mag, mag).view(nblocks, block)
+
+
 def mxfp4_dequantize_reference(payload: torch.Tensor, sbytes: torch.Tensor, n: int,
                                dtype: torch.dtype) -> torch.Tensor:
     """``q * 2^k`` exact in fp32, then one rounding to ``dtype``; a block with
     the NaN scale byte restores as positive quiet NaNs."""
     nblocks = sbytes.numel()
-    p = payload[: (n + 1) // 2]
-    codes = torch.zeros(nblocks * MX_BLOCK, dtype=torch.uint8, device=p.device)
-    codes[0: 2 * p.numel(): 2] = p & 0xF
-    codes[1: 2 * p.numel(): 2] = p >> 4
-    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=p.device)[(codes & 7).long()]
-    q = torch.where((codes & 8) != 0, -mag, mag).view(nblocks, MX_BLOCK)
+    q = _e2m1_decode(payload, n, nblocks, MX_BLOCK)
     is_nan = sbytes == E8M0_NAN
     k = torch.where(is_nan, torch.zeros_like(sbytes), sbytes).to(torch.int32) - 127
     out = (q * pow2(k)[:, None]).reshape(-1)[:n].to(dtype)
     # the NaN by its bits: a cast of NaN picks its own sign and payload
     view, bits = _QUIET_NAN_BITS[dtype]
     out.view(view)[is_nan.repeat_interleave(MX_BLOCK)[:n]] = bits
+    return out
+
+
+NVFP4_TOP = 2688.0  # 448 * 6: the largest e4m3 scale times the largest e2m1 magnitude
+NVFP4_MIN_TS = 2.0 ** -117  # floor of the tensor scale: ts * 2^-9 >= 2^-126
+E4M3_NAN = 0x7F
+
+
+def nvfp4_tensor_scale(amax: torch.Tensor) -> torch.Tensor:
+    """``ts = max(A / 2688, 2^-117)`` in fp32 (tensor / tensor: correctly
+    rounded, see ``_scale_and_quant``)."""
+    return torch.maximum(amax / torch.full_like(amax, NVFP4_TOP),
+                         torch.full_like(amax, NVFP4_MIN_TS))
+
+
+def nvfp4_quantize_reference(x: torch.Tensor):
+    """Two-level-scaled FP4 reference: returns (payload[round_up(ceil(n / 2),
+    16)] uint8 in the ``mxfp4`` nibble order, scale bytes[ceil(n / 16)] uint8
+    (e4m3fn), amax[1] float32).  The rules are in the module docstring; every
+    line below is one fp32 operation of them."""
+    flat = x.detach().reshape(-1).float()
+    n = flat.numel()
+    nblocks = (n + NV_BLOCK - 1) // NV_BLOCK
+    blocks = torch.zeros(nblocks * NV_BLOCK, dtype=torch.float32, device=flat.device)
+    blocks[:n] = flat
+    blocks = blocks.view(nblocks, NV_BLOCK)
+    a = blocks.abs()
+    finite_a = torch.where(torch.isfinite(a), a, torch.zeros_like(a))
+    amax = finite_a.amax().reshape(1)
+    ts = nvfp4_tensor_scale(amax)
+    quot = finite_a.amax(dim=1) / (torch.full_like(ts, 6.0) * ts)
+    s8 = torch.minimum(quot, torch.full_like(quot, FP8_MAX)).to(torch.float8_e4m3fn)
+    d = s8.float() * ts
+    inv = torch.ones_like(d) / d  # inf where s8 == 0
+    y = (a * inv[:, None]).clamp(max=6.0)  # on magnitudes: rounding is symmetric; inf -> 6
+    idx = torch.where((d > 0)[:, None], _e2m1_index(y), torch.zeros_like(y, dtype=torch.uint8))
+    codes = idx | (torch.signbit(blocks).to(torch.uint8) << 3)
+    has_nan = torch.isnan(blocks).any(dim=1)
+    codes = torch.where(has_nan[:, None], torch.zeros_like(codes), codes).reshape(-1)
+    sbytes = torch.where(has_nan, torch.full_like(has_nan, E4M3_NAN, dtype=torch.uint8),
+                         s8.view(torch.uint8))
+    payload = torch.zeros(nvfp4_payload_bytes(n), dtype=torch.uint8, device=flat.device)
+    payload[: (n + 1) // 2] = (codes[0::2] | (codes[1::2] << 4))[: (n + 1) // 2]
+    return payload, sbytes, amax
+
+
+def nvfp4_dequantize_reference(payload: torch.Tensor, sbytes: torch.Tensor, amax: torch.Tensor,
+                               n: int, dtype: torch.dtype) -> torch.Tensor:
+    """``q * d`` with ``d = f32(s8) * ts``, two fp32 products, then one rounding
+    to ``dtype``; a block with the e4m3fn NaN byte restores as positive quiet
+    NaNs."""
+    nblocks = sbytes.numel()
+    q = _e2m1_decode(payload, n, nblocks, NV_BLOCK)
+    is_nan = (sbytes & 0x7F) == E4M3_NAN
+    s8 = torch.where(is_nan, torch.zeros_like(sbytes), sbytes).view(torch.float8_e4m3fn)
+    d = s8.float() * nvfp4_tensor_scale(amax.reshape(1).float())
+    out = (q * d[:, None]).reshape(-1)[:n].to(dtype)
+    view, bits = _QUIET_NAN_BITS[dtype]
+    out.view(view)[is_nan.repeat_interleave(NV_BLOCK)[:n]] = bits
     return out
 
 
@@ -624,7 +765,7 @@ def stage_fp8(t: torch.Tensor, entry: TensorEntry, producer: int) -> StagedBuffe
     info = entry.quant
     rot = info.get("rotation", "none")
     payload, nblocks, total = info["payload_bytes"], info["nblocks"], info["total_bytes"]
-    if is_mx(info) or is_mxfp4(info) or is_mxfp6(info):
+    if is_mx(info) or is_mxfp4(info) or is_mxfp6(info) or is_nvfp4(info):
         return _stage_mx(t, info, producer)
     if t.is_cuda:
         from ..engine import staging
@@ -661,8 +802,10 @@ def stage_fp8(t: torch.Tensor, entry: TensorEntry, producer: int) -> StagedBuffe
 
 def _stage_mx(t: torch.Tensor, info: Dict[str, Any], producer: int) -> StagedBuffer:
     """The E8M0 layouts: MX fp8, MXFP6, MXFP4 and rotated MXFP4 (same blob
-    shape, other kernel)."""
+    shape, other kernel), and the two-level-scaled FP4 one, whose scale bytes
+    are padded to a multiple of 4 and followed by the fp32 amax."""
     payload, total = info["payload_bytes"], info["total_bytes"]
+    nv = is_nvfp4(info)
     fp4h = is_mxfp4_hadamard(info)
     fp4 = is_mxfp4(info) and not fp4h
     fp6 = is_mxfp6(info)
@@ -679,17 +822,26 @@ def _stage_mx(t: torch.Tensor, info: Dict[str, Any], producer: int) -> StagedBuf
             stream.wait_event(ev)
         src = t if t.is_contiguous() else t.contiguous()
         blob = torch.empty(total, dtype=torch.uint8, device=t.device)  # kernel writes all of it
+        if nv:
+            native.nvfp4_quantize(dev, src, blob[:payload], blob[payload: total - 4],
+                                  blob[total - 4:], int(stream.cuda_stream))
+            return staging.d2h_tensor(blob, int(stream.cuda_stream))
         quantize = (native.mxfp4_hadamard_quantize if fp4h else
                     native.mxfp4_quantize if fp4 else
                     native.mxfp6_quantize if fp6 else native.mx8_quantize)
         quantize(dev, src, blob[:payload], blob[payload:], int(stream.cuda_stream))
         return staging.d2h_tensor(blob, int(stream.cuda_stream))
-    q, sbytes = (mxfp4_hadamard_quantize_reference(t) if fp4h else
-                 mxfp4_quantize_reference(t) if fp4 else
-                 mxfp6_quantize_reference(t) if fp6 else mx_quantize_reference(t))
+    if nv:
+        q, sbytes, amax = nvfp4_quantize_reference(t)
+    else:
+        q, sbytes = (mxfp4_hadamard_quantize_reference(t) if fp4h else
+                     mxfp4_quantize_reference(t) if fp4 else
+                     mxfp6_quantize_reference(t) if fp6 else mx_quantize_reference(t))
     blob = torch.zeros(total, dtype=torch.uint8)
     blob[: q.numel()] = q.view(torch.uint8)
-    blob[payload:] = sbytes
+    blob[payload: payload + sbytes.numel()] = sbytes
+    if nv:
+        blob[total - 4:] = amax.view(torch.uint8)
     from ..format.serialization import contiguous_cpu_bytes_view
 
     return StagedBuffer(contiguous_cpu_bytes_view(blob), keepalive=blob)
@@ -713,6 +865,11 @@ def dequantize_host_fp8(buf, entry: TensorEntry) -> torch.Tensor:
     mv = memoryview(buf.view if isinstance(buf, StagedBuffer) else buf).cast("B")
     raw = torch.frombuffer(bytearray(mv[: info["total_bytes"]]), dtype=torch.uint8)
     dtype = string_to_dtype(entry.dtype)
+    if is_nvfp4(info):
+        p, total = info["payload_bytes"], info["total_bytes"]
+        out = nvfp4_dequantize_reference(raw[:p], raw[p: p + info["nblocks"]],
+                                         raw[total - 4: total].view(torch.float32), n, dtype)
+        return out.view(list(entry.shape))
     if is_mxfp6(info):
         p = info["payload_bytes"]
         out = mxfp6_dequantize_reference(raw[:p], raw[p: p + info["nblocks"]], n, dtype)
@@ -745,6 +902,11 @@ def dequantize_device(blob_dev: torch.Tensor, entry: TensorEntry, dst: torch.Ten
     n = dst.numel()
     stream = int(torch.cuda.current_stream(dst.device).cuda_stream)
     dev = dst.device.index or 0
+    if is_nvfp4(info):
+        p, total = info["payload_bytes"], info["total_bytes"]
+        native.nvfp4_dequantize(dev, blob_dev[:p], blob_dev[p: p + info["nblocks"]],
+                                blob_dev[total - 4: total], dst, stream)
+        return
     if is_mxfp6(info):
         p = info["payload_bytes"]
         native.mxfp6_dequantize(dev, blob_dev[:p], blob_dev[p: p + info["nblocks"]], dst, stream)

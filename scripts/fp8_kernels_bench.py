@@ -1,16 +1,19 @@
 """fp8 quantize / dequantize kernels alone on 512 Mi elements (1 GiB of bf16;
+``--mi-elems M`` for another size;
 for rocprofv3 --stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128,
 MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32), Hadamard-rotated MXFP4,
-MXFP6 (e2m3 codes, E8M0 per 32).
+MXFP6 (e2m3 codes, E8M0 per 32), two-level-scaled FP4 (e2m1 nibbles, e4m3 per
+16 under one fp32 scale; its quantize is three launches and reads the source
+twice, and ``traffic_bytes`` counts that).
 Prints one JSON line per
 kernel with host-timed GB/s of HBM traffic (read + written bytes), the time
 between device events around the call, and GB/s of the tensor alone (source
 bytes of a quantize, destination bytes of a dequantize).
 
-    fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [mode ...]
+    fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [--mi-elems M] [mode ...]
 
 Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``, ``mxfp4_hadamard32``,
-``mxfp6``.  ``--rounds R`` goes
+``mxfp6``, ``nvfp4``.  ``--rounds R`` goes
 through the list of modes R times, so that two modes alternate and the spread
 of one mode's repeats is seen beside the difference between the two.
 
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
     ap.add_argument("--offset", action="store_true")
     ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--mi-elems", type=int, default=512)
     ap.add_argument("modes", nargs="*", default=["mx_e8m0", "none", "hadamard32"])
     args = ap.parse_args()
     dev = 0
@@ -59,13 +63,13 @@ def main():
     modes = args.modes * args.rounds
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     off = 1 if args.offset else 0
-    nw = 512 << 20
+    nw = args.mi_elems << 20
     w = torch.empty(nw + off, dtype=dtype, device="cuda:0").normal_()[off:]
     hs = int(torch.cuda.current_stream().cuda_stream)
     for mode in modes:
         if mode == "mx_e8m0":
             info = quant.fp8_entry_quant_info(w, rotation="none")
-        elif mode in ("mxfp4", "mxfp4_hadamard32", "mxfp6"):
+        elif mode in ("mxfp4", "mxfp4_hadamard32", "mxfp6", "nvfp4"):
             os.environ["HIPSNAPSHOT_FP8_FORMAT"] = mode
             info = quant.fp8_entry_quant_info(w, rotation=None if "hadamard" in mode else "none")
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
@@ -75,7 +79,7 @@ def main():
             del os.environ["HIPSNAPSHOT_FP8_FORMAT"]
         blob = torch.zeros(info["total_bytes"], dtype=torch.uint8, device="cuda:0")
         p = info["payload_bytes"]
-        e8m0 = mode in ("mx_e8m0", "mxfp4", "mxfp4_hadamard32", "mxfp6")
+        e8m0 = mode in ("mx_e8m0", "mxfp4", "mxfp4_hadamard32", "mxfp6", "nvfp4")  # byte scales
         sc = blob[p:] if e8m0 else blob[p:].view(torch.float32)
         back = torch.empty(nw + off, dtype=dtype, device="cuda:0")[off:]
         if mode == "mx_e8m0":
@@ -84,6 +88,10 @@ def main():
         elif mode == "mxfp4":
             q = lambda: native.mxfp4_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mxfp4_dequantize(dev, blob[:p], sc, back, hs)  # noqa: E731
+        elif mode == "nvfp4":
+            sc, am = blob[p: -4], blob[-4:]
+            q = lambda: native.nvfp4_quantize(dev, w, blob[:p], sc, am, hs)  # noqa: E731
+            dq = lambda: native.nvfp4_dequantize(dev, blob[:p], sc, am, back, hs)  # noqa: E731
         elif mode == "mxfp6":
             q = lambda: native.mxfp6_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.mxfp6_dequantize(dev, blob[:p], sc, back, hs)  # noqa: E731
@@ -96,14 +104,15 @@ def main():
         else:
             q = lambda: native.fp8_hadamard_quantize(dev, w, blob[:p], sc, hs)  # noqa: E731
             dq = lambda: native.fp8_hadamard_dequantize(dev, blob[:p], sc, back, hs)  # noqa
-        traffic = nw * w.element_size() + info["total_bytes"]
         for name, fn in (("quant", q), ("dequant", dq)):
+            reads = 2 if (mode, name) == ("nvfp4", "quant") else 1
+            traffic = reads * nw * w.element_size() + info["total_bytes"]
             best, med, ev_best, ev_med = timeit(fn)
             tensor = nw * w.element_size()
             print(json.dumps({"kernel": f"{name}_{mode}", "ms_best": round(best * 1e3, 4),
                               "TBps_best": round(traffic / best / 1e12, 3),
                               "TBps_median": round(traffic / med / 1e12, 3),
-                              "traffic_bytes": traffic,
+                              "traffic_bytes": traffic, "elems": nw,
                               "event_ms_best": round(ev_best * 1e3, 4),
                               "event_ms_median": round(ev_med * 1e3, 4),
                               "tensor_GBps_event_median": round(tensor / ev_med / 1e9, 1)}),
