@@ -111,6 +111,9 @@ int hsg_nvfp4_quantize(int dev, const void* src, int src_dtype, int64_t n, void*
                        void* scales, void* amax, void* stream);
 int hsg_nvfp4_dequantize(int dev, const void* q, const void* scales, const void* amax, int64_t n,
                          void* dst, int dst_dtype, void* stream);
+uint64_t hsg_quant_probe_out_bytes();
+int hsg_quant_probe(int dev, const void* src, int src_dtype, int64_t n, int candidates_mask,
+                    void* out, void* stream);
 
 // hsgpu.hip: managed memory, stream gate
 int hsg_is_managed(const void* p);

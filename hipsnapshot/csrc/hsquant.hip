@@ -1964,6 +1964,313 @@ hs_mxfp4_hadamard_dequant(const uint8_t* __restrict__ q, const uint8_t* __restri
 }
 
 // ---------------------------------------------------------------------------
+// Format probe (hs_quant_probe): what would each of the four un-rotated
+// layouts lose on this tensor?  One read of the source, no payload.  For a
+// format F with restore r_F into fp32 (ops/quant.py format_errors_reference
+// states the sums once):
+//   sumsq = sum x^2 and n_finite over the finite x; err2_F = sum (x - r_F)^2
+//   over the elements where x and r_F are finite; spoiled_F = the number of
+//   finite x whose r_F is not (the finite neighbours of a NaN in a NaN block,
+//   the fp32-overflow edge of a code that rounds up).
+// Work split: hs_mxfp4_quant's stream -- wave-contiguous 16-B loads, kStreamU
+// in flight per lane, a grid-stride over chunks.  A lane's finite amax key
+// (fp4_lane_key without the NaN key: MX fp8 keeps a NaN in its own element,
+// so the block's finite amax is needed beside the NaN flag) is joined over
+// the quad by DPP moves: after the step that covers 16 elements it is the
+// two-level format's sub-block key, one step later the 32-block's, from whose
+// one frexp the three E8M0 exponents (448, 7.5, 6) follow.  The NaN flags of
+// the 16- and the 32-block take the same steps, but only in a wave that holds
+// a non-finite value at all (one ballot).
+// Round trips, all in registers, element for element the rules above:
+//   * MX fp8: v_ldexp_f32, v_cvt_pk_fp8_f32, v_cvt_f32_fp8, v_ldexp_f32;
+//   * MXFP4: the scaled fp4 conversion of the source words (fp4_pack), back
+//     through v_cvt_scalef32_pk_f32_fp4 at scale 1 and v_ldexp_f32;
+//   * two-level FP4: hs_nvfp4_quant's two divisions per block, v_med3_f32,
+//     the fp4 conversion at scale 1, the decode and one product with d;
+//   * MXFP6: gfx950 converts e2m3 a whole block at a time, which wants a lane
+//     to own a block (hs_mxfp6_quant goes through LDS for that), while every
+//     other step here wants a block across 4 or 8 lanes.  So the scaled value
+//     is rounded to the e2m3 grid arithmetically: |y| <= 7.5 has the grid's
+//     step 2^(max(e, 0) - 3) for |y| in [2^e, 2^(e + 1)), and (|y| + C) - C
+//     with C = 2^(max(e, 0) + 20) is fp32's own round to nearest, ties to the
+//     even multiple of that step, which is the even index (every segment of
+//     the grid starts at an even index, a tie at a segment's end goes to the
+//     next power of two).  Two additions and three integer operations per
+//     element, no LDS, no second layout of the data.
+// An element past n is a zero and an element that is not finite takes no part
+// in any sum, so what its round trips give does not matter.
+// Accumulation: e = x - r in fp32 (one rounding; finite for finite x and r,
+// which have one sign), widened, squared and added in f64: first the lane's 8
+// or 4 elements of a load, then, if that partial sum is finite (no x or r was
+// not), into the lane's total.  Otherwise the elements go one by one under the
+// mask of the lane's finite elements, which is also what is counted.  f64
+// never overflows on fp32 squares; fp32 squares of bf16 values would.
+// Reduction, in a fixed order: lanes by xor-shuffle, the workgroup's waves
+// through LDS in wave order, each workgroup's ten partials into its own row of
+// the scratch area behind the report (vector stores), then hs_quant_probe_sum,
+// one wave per column, adds the rows: lane l rows l, l + 64, ..., then the
+// same shuffle tree.  No atomics; the grid depends on n and the dtype only, so
+// the report is a function of the tensor's bytes.
+// ---------------------------------------------------------------------------
+
+constexpr int kProbeMxfp4 = 1, kProbeNvfp4 = 2, kProbeMxfp6 = 4, kProbeMx8 = 8;  // candidates_mask
+constexpr int kProbeFormats = 4;                // columns in that order: by size
+constexpr int kProbeCols = 2 + 2 * kProbeFormats;  // sumsq, err2[4] (f64); n_finite, spoiled[4] (u64)
+constexpr int kProbeAmaxWord = kProbeCols;      // low half: the tensor's amax A (f32)
+constexpr int kProbeRowWords = 16;              // 8-byte words of a row: the report, then a row per workgroup
+constexpr int kProbeGrid = 1024;                // workgroups at most
+
+// one load's restored values `r` of format F against its sources `v`; `fin`:
+// bit j set where element j is inside the tensor and finite
+template <int EPL>
+__device__ __forceinline__ void probe_add(const float* v, const float* r, uint32_t fin,
+                                          double& err2, uint32_t& spoiled) {
+  float e[EPL];
+  double part = 0.;
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) {
+    e[j] = v[j] - r[j];
+    part = __builtin_fma(static_cast<double>(e[j]), static_cast<double>(e[j]), part);
+  }
+  if (part < __builtin_huge_val()) {  // every x and r finite (an element past n: 0 - 0)
+    err2 += part;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) {
+    if (!((fin >> j) & 1u)) continue;
+    if (fabsf(e[j]) < __builtin_huge_valf())
+      err2 = __builtin_fma(static_cast<double>(e[j]), static_cast<double>(e[j]), err2);
+    else
+      ++spoiled;
+  }
+}
+
+// lane ^ o's `v`: a DPP quad move inside a quad, a wave shuffle beyond
+__device__ __forceinline__ uint32_t probe_xor(uint32_t v, int o) {
+  if (o == 1) return static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(int(v), 0xB1, 0xF, 0xF, false));
+  if (o == 2) return static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(int(v), 0x4E, 0xF, 0xF, false));
+  return static_cast<uint32_t>(__shfl_xor(int(v), o, 64));
+}
+
+// the wave's sum in every lane, by the xor tree: one order whatever the values
+template <class T>
+__device__ __forceinline__ T probe_wave_sum(T v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    if constexpr (std::is_same<T, double>::value) v += __shfl_xor(v, o, 64);
+    else v += static_cast<T>(__shfl_xor(static_cast<long long>(v), o, 64));
+  }
+  return v;
+}
+
+template <int DT>
+__global__ void HS_NO_PK_F32 __launch_bounds__(kBlock)
+hs_quant_probe(const char* __restrict__ src, int64_t n, int mask,
+               const uint32_t* __restrict__ amax, uint64_t* __restrict__ rows) {
+  constexpr int ES = (DT == kF32) ? 4 : 2;
+  constexpr int EPL = 16 / ES;    // elements per lane per load
+  constexpr int LPB = 32 / EPL;   // lanes of a 32-block: 4 or 8
+  constexpr int U = kStreamU;
+  constexpr int64_t kChunk = 64LL * EPL * U;
+  constexpr uint32_t kAll = (1u << EPL) - 1;
+  __shared__ uint64_t wave_part[kBlock / 64][kProbeCols];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t wave0 = int64_t(blockIdx.x) * (kBlock / 64) + wave;  // scalar
+  const int64_t nwaves = (int64_t(gridDim.x) * kBlock) >> 6;
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+  const bool want4 = mask & kProbeMxfp4, wantnv = mask & kProbeNvfp4;
+  const bool want6 = mask & kProbeMxfp6, want8 = mask & kProbeMx8;
+  const float ts = wantnv ? nvfp4_tensor_scale(__uint_as_float(*amax)) : 1.f;
+  const float six_ts = 6.f * ts;
+  double sumsq = 0., err2_4 = 0., err2_nv = 0., err2_6 = 0., err2_8 = 0.;
+  uint32_t n_finite = 0, bad_4 = 0, bad_nv = 0, bad_6 = 0, bad_8 = 0;  // of this lane
+  for (int64_t base = wave0 * kChunk; base < n; base += nwaves * kChunk) {
+    const bool full = aligned && base + kChunk <= n;
+    mx_u32x4 raw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+      raw[u] = full ? __builtin_nontemporal_load(reinterpret_cast<const mx_u32x4*>(src + e0 * ES))
+                    : load16_elems<ES>(src, e0, n);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const mx_u32x4 w = raw[u];
+      bool nonfinite;
+      uint32_t key32 = fp4_lane_key<DT, false>(w, nonfinite);
+      uint32_t key16 = 0;
+#pragma unroll
+      for (int o = 1; o < LPB; o <<= 1) {
+        key32 = max(key32, probe_xor(key32, o));
+        if (2 * o == LPB / 2) key16 = key32;  // 16 elements joined: the two-level sub-block
+      }
+      // the lane's finite elements inside the tensor, and its blocks' NaN flags
+      uint32_t fin = kAll;
+      bool nan16 = false, nan32 = false;
+      if (!full) {
+        const int64_t e0 = base + (int64_t(u) * 64 + lane) * EPL;
+        const int64_t left = n - e0;
+        fin = left >= EPL ? kAll : (left > 0 ? (1u << left) - 1 : 0u);
+      }
+      if (__builtin_amdgcn_ballot_w64(nonfinite) != 0) {  // rare, wave-uniform
+        uint32_t nan = 0;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) {
+          const uint32_t p = fp4_abs_bits<DT>(w, j);
+          if (p >= kInfBits<DT>) fin &= ~(1u << j);
+          if (p > kInfBits<DT>) nan = 1;
+        }
+#pragma unroll
+        for (int o = 1; o < LPB; o <<= 1) {
+          nan |= probe_xor(nan, o);
+          if (2 * o == LPB / 2) nan16 = nan;
+        }
+        nan32 = nan;
+      }
+      n_finite += __popc(fin);
+      float v[EPL], r[EPL];
+      unpack16<DT>(w, v);
+      {
+        double part = 0.;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j)
+          part = __builtin_fma(static_cast<double>(v[j]), static_cast<double>(v[j]), part);
+        if (part < __builtin_huge_val()) {
+          sumsq += part;
+        } else {
+#pragma unroll
+          for (int j = 0; j < EPL; ++j)
+            if ((fin >> j) & 1u)
+              sumsq = __builtin_fma(static_cast<double>(v[j]), static_cast<double>(v[j]), sumsq);
+        }
+      }
+      // the three E8M0 exponents from one frexp of the block's amax
+      int k8 = 0, k6 = 0, k4 = 0;
+      const float bamax = fp4_key_value<DT>(key32);
+      if (bamax > 0.f) {
+        int e;
+        const float m = frexpf(bamax, &e);
+        k8 = max(-127, min(127, m <= 0.875f ? e - 9 : e - 8));
+        k6 = max(-127, min(127, m <= 0.9375f ? e - 3 : e - 2));
+        k4 = max(-127, min(127, m <= 0.75f ? e - 3 : e - 2));
+      }
+      const float qnan = __builtin_nanf("");
+      if (want4) {
+        const uint32_t code = fp4_pack<DT>(w, uint32_t(k4 + 127), false);
+        mx_f32x2 p[EPL / 2];  // the byte select must be an immediate
+        p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 0);
+        p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 1);
+        if constexpr (EPL == 8) {
+          p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 2);
+          p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 3);
+        }
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) r[j] = nan32 ? qnan : ldexpf(p[j >> 1][j & 1], k4);
+        probe_add<EPL>(v, r, fin, err2_4, bad_4);
+      }
+      if (wantnv) {
+        const float quot = fminf(fp4_key_value<DT>(key16) / six_ts, kFp8Max);
+        const int s8 = __builtin_amdgcn_cvt_pk_fp8_f32(quot, 0.f, 0, false);
+        const float d = __builtin_amdgcn_cvt_f32_fp8(s8, 0) * ts;
+        const float inv = d > 0.f ? 1.f / d : 0.f;  // d == 0: the block restores as zeros
+        float y[EPL];
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) y[j] = __builtin_amdgcn_fmed3f(v[j] * inv, -6.f, 6.f);
+        uint32_t code = 0;
+        code = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(code, y[0], y[1], 1.0f, 0);
+        code = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(code, y[2], y[3], 1.0f, 1);
+        if constexpr (EPL == 8) {
+          code = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(code, y[4], y[5], 1.0f, 2);
+          code = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(code, y[6], y[7], 1.0f, 3);
+        }
+        mx_f32x2 p[EPL / 2];
+        p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 0);
+        p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 1);
+        if constexpr (EPL == 8) {
+          p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 2);
+          p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code, 1.0f, 3);
+        }
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) r[j] = nan16 ? qnan : p[j >> 1][j & 1] * d;
+        probe_add<EPL>(v, r, fin, err2_nv, bad_nv);
+      }
+      if (want6) {
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) {
+          const uint32_t a = __float_as_uint(ldexpf(v[j], -k6)) & 0x7fffffffu;
+          const float c = __uint_as_float((max(a >> 23, 127u) + 20u) << 23);
+          const float q = (__uint_as_float(a) + c) - c;
+          r[j] = nan32 ? qnan : copysignf(ldexpf(q, k6), v[j]);
+        }
+        probe_add<EPL>(v, r, fin, err2_6, bad_6);
+      }
+      if (want8) {
+        float y[EPL];
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) y[j] = ldexpf(v[j], -k8);
+#pragma unroll
+        for (int i = 0; i < EPL / 4; ++i) {
+          int word = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * i], y[4 * i + 1], 0, false);
+          word = __builtin_amdgcn_cvt_pk_fp8_f32(y[4 * i + 2], y[4 * i + 3], word, true);
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            r[4 * i + b] = ldexpf(fp8_byte_to_f32(static_cast<uint32_t>(word), b), k8);
+        }
+        probe_add<EPL>(v, r, fin, err2_8, bad_8);
+      }
+    }
+  }
+  // lanes, then waves, then this workgroup's row
+  const double f[1 + kProbeFormats] = {probe_wave_sum(sumsq), probe_wave_sum(err2_4),
+                                       probe_wave_sum(err2_nv), probe_wave_sum(err2_6),
+                                       probe_wave_sum(err2_8)};
+  const uint64_t c[1 + kProbeFormats] = {
+      probe_wave_sum(uint64_t(n_finite)), probe_wave_sum(uint64_t(bad_4)),
+      probe_wave_sum(uint64_t(bad_nv)), probe_wave_sum(uint64_t(bad_6)),
+      probe_wave_sum(uint64_t(bad_8))};
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i <= kProbeFormats; ++i) {
+      wave_part[wave][i] = __builtin_bit_cast(uint64_t, f[i]);
+      wave_part[wave][1 + kProbeFormats + i] = c[i];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kProbeCols) {
+    const int col = threadIdx.x;
+    uint64_t word;
+    if (col <= kProbeFormats) {
+      double s = 0.;
+      for (int i = 0; i < kBlock / 64; ++i) s += __builtin_bit_cast(double, wave_part[i][col]);
+      word = __builtin_bit_cast(uint64_t, s);
+    } else {
+      word = 0;
+      for (int i = 0; i < kBlock / 64; ++i) word += wave_part[i][col];
+    }
+    rows[int64_t(blockIdx.x) * kProbeRowWords + col] = word;
+  }
+}
+
+// one wave per column: report[col] = the sum of rows[0 .. nrows)[col]
+__global__ void __launch_bounds__(64)
+hs_quant_probe_sum(const uint64_t* __restrict__ rows, int nrows, uint64_t* __restrict__ report) {
+  const int col = blockIdx.x;
+  const int lane = threadIdx.x;
+  double f = 0.;
+  uint64_t c = 0;
+  for (int row = lane; row < nrows; row += 64) {
+    const uint64_t word = rows[int64_t(row) * kProbeRowWords + col];
+    if (col <= kProbeFormats) f += __builtin_bit_cast(double, word);
+    else c += word;
+  }
+  f = probe_wave_sum(f);
+  c = probe_wave_sum(c);
+  if (lane == 0) report[col] = col <= kProbeFormats ? __builtin_bit_cast(uint64_t, f) : c;
+}
+
+// ---------------------------------------------------------------------------
 // Host dispatch: a runtime dtype code or vpt becomes a template argument by
 // calling `f` with an integral_constant of it; kNoKernel where none fits.
 // ---------------------------------------------------------------------------
@@ -2228,6 +2535,57 @@ int hsg_mxfp4_hadamard_dequantize(int dev, const void* q, const void* scales, in
                   scales, n, nblocks, dst);
   });
   return rc == kNoKernel ? unsupported_dtype("mxfp4 hadamard dest", dst_dtype) : rc;
+}
+
+// bytes of the `out` buffer of hsg_quant_probe: the report row, then a row of
+// partial sums per workgroup
+uint64_t hsg_quant_probe_out_bytes() {
+  return uint64_t(1 + kProbeGrid) * kProbeRowWords * 8;
+}
+
+// Format probe: src (bf16/f16/f32, contiguous, n elements) -> the first 11
+// 8-byte words of `out` (device memory, 8-byte aligned, hsg_quant_probe_out_
+// bytes() long): sumsq and err2 of mxfp4, nvfp4, mxfp6, mx as f64; n_finite and
+// spoiled of the same four as u64; the tensor's finite amax as an f32 in the
+// low half of word 10 (only with the nvfp4 candidate).  `candidates_mask`: bit
+// 0 mxfp4, 1 nvfp4, 2 mxfp6, 3 mx; the columns of the others are 0.  Launches
+// on `stream` (clear and amax for nvfp4, probe, sum); copying the words to the
+// host and waiting for them is the caller's.
+int hsg_quant_probe(int dev, const void* src, int src_dtype, int64_t n, int candidates_mask,
+                    void* out, void* stream) {
+  HS_CHECK(hipSetDevice(dev));
+  if (reinterpret_cast<uintptr_t>(out) & 7) {
+    hs_set_error("quant probe buffer %p is not 8-byte aligned", out);
+    return -1004;
+  }
+  if (candidates_mask <= 0 || candidates_mask >= (1 << kProbeFormats)) {
+    hs_set_error("quant probe candidates mask %d", candidates_mask);
+    return -1005;
+  }
+  uint64_t* report = static_cast<uint64_t*>(out);
+  uint64_t* rows = report + kProbeRowWords;
+  uint32_t* amax = reinterpret_cast<uint32_t*>(report + kProbeAmaxWord);
+  const int grid = n > 0 ? grid_for(n, stream_chunk(src_dtype), kProbeGrid) : 0;
+  const int rc = for_dtype<false>(src_dtype, [&](auto dt) {
+    constexpr int kDt = decltype(dt)::value;
+    int r = 0;
+    if (n > 0 && (candidates_mask & kProbeNvfp4)) {
+      r = launch(hs_nvfp4_clear, 1, stream, amax);
+      if (r == 0)
+        r = launch(hs_nvfp4_amax<kDt>,
+                   grid_for(n, stream_chunk(src_dtype) / kStreamU * kAmaxU, kAmaxGrid), stream,
+                   src, n, amax);
+    }
+    if (r == 0 && n > 0)
+      r = launch(hs_quant_probe<kDt>, grid, stream, src, n, candidates_mask, amax, rows);
+    return r;
+  });
+  if (rc == kNoKernel) return unsupported_dtype("quant probe source", src_dtype);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(hs_quant_probe_sum, dim3(kProbeCols), dim3(64), 0,
+                     static_cast<hipStream_t>(stream), rows, grid, report);
+  HS_CHECK(hipGetLastError());
+  return 0;
 }
 
 // Hadamard-rotated fp8: payload `out` has n_pad = round_up(n, 32) bytes,

@@ -81,10 +81,21 @@ class TensorIOPreparer:
                 f"(changed from {tensor.shape} to {proc.shape}).")
         quant = None
         if serializer == SER.FP8_BLOCK:
-            from ..ops.quant import fp8_entry_quant_info, fp8_supported
+            from .. import knobs
+            from ..ops.quant import auto_format, fp8_entry_quant_info, fp8_supported
 
             if not fp8_supported(proc):
                 serializer = None
+            elif knobs.fp8_format() == "auto":
+                # measured now, on the caller's current stream (before an async
+                # take's freeze): every written piece chooses for itself
+                fmt, rel = auto_format(proc)
+                if fmt is None:
+                    serializer = None  # nothing within the budget: written as it is
+                else:
+                    quant = fp8_entry_quant_info(proc, fmt=fmt)
+                    quant["rel_l2"] = rel
+                    quant["selected"] = "auto"
             else:
                 quant = fp8_entry_quant_info(proc)
         if serializer is None:

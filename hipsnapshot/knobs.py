@@ -17,7 +17,7 @@ docs/getting_started.md): the reference's five, then
 * distributed: ``REBALANCE``, ``STATE_DICT_BARRIERS``, ``FORCE_COLLECTIVES``;
 * host: ``NUMA_BIND``, ``PINNED_POOL_MAX_BYTES``;
 * format: ``FP8_FORMAT`` (``mx`` | ``block`` | ``hadamard32`` | ``mxfp4`` |
-  ``mxfp4_hadamard32`` | ``mxfp6`` | ``nvfp4``);
+  ``mxfp4_hadamard32`` | ``mxfp6`` | ``nvfp4`` | ``auto[:max_error[:formats]]``);
 * tracing: ``TIMELINE``, ``ROCTX``.
 
 Everything else that used to be an environment switch -- engine sizing,
@@ -227,6 +227,11 @@ class _Tuning:
     content_digests = False
     gc_after_plan = True       # one full GC pass after a take that built a plan
     plan_cache = True          # reuse a take's plan (engine/plan_cache.py)
+    # FP8_FORMAT=auto (ops/quant.py format_errors): the relative L2 error a
+    # tensor may lose -- a policy choice, "about the quality of fp8", not a
+    # measurement -- and the formats it may get
+    quant_max_error = 0.03
+    quant_auto_formats = "mxfp4,nvfp4,mxfp6,mx"
     # async takes drain the frozen device state raw: the encoder on the CUs
     # beside a training step cost +30 % step time (profiles/overlap_iso/)
     async_device_codec = "raw"
@@ -620,10 +625,53 @@ def fp8_format() -> str:
     bits per element at about the error of ``mx``), ``nvfp4`` (e2m1 nibbles +
     e4m3 scale per 16 elements + one fp32 scale for the tensor: 4.5 bits per
     element, 18 to 50 % less error than ``mxfp4``; not for tensors whose
-    magnitudes span more than about 2^20, such as Adam second moments)."""
-    v = str(_get("FP8_FORMAT") or "mx").strip().lower()
+    magnitudes span more than about 2^20, such as Adam second moments),
+    ``auto`` (every written tensor is probed and gets the smallest of
+    ``quant_auto_formats()`` whose measured relative L2 error is within
+    ``quant_max_error()``, or stays unquantized: ops/quant.py
+    ``format_errors``)."""
+    v = _fp8_format_fields()[0]
     return v if v in ("mx", "block", "hadamard32", "mxfp4", "mxfp4_hadamard32", "mxfp6",
-                      "nvfp4") else "mx"
+                      "nvfp4", "auto") else "mx"
+
+
+def _fp8_format_fields() -> list:
+    """``FP8_FORMAT`` cut at its colons: ``auto[:max_error[:formats]]``."""
+    return [p.strip() for p in str(_get("FP8_FORMAT") or "mx").lower().split(":")]
+
+
+AUTO_FORMATS = ("mxfp4", "nvfp4", "mxfp6", "mx")  # the candidates of ``auto``, by size
+
+
+def quant_max_error() -> float:
+    """The relative L2 error ``|restored - x| / |x|`` a tensor may lose under
+    ``FP8_FORMAT=auto``: ``TUNING.quant_max_error``, or the second field of
+    ``FP8_FORMAT=auto:0.05``.  The default 0.03 is a policy choice, not a
+    measurement: "about the quality of fp8" (``mx`` measures 0.027 and
+    ``mxfp6`` 0.028 on Gaussian data), so that ``auto`` by default writes no
+    tensor visibly worse than the default format would."""
+    fields = _fp8_format_fields()
+    if fields[0] == "auto" and len(fields) > 1 and fields[1]:
+        try:
+            v = float(fields[1])
+            if v >= 0:
+                return v
+        except ValueError:
+            pass
+    return float(_tuned("quant_max_error"))
+
+
+def quant_auto_formats() -> tuple:
+    """The formats ``auto`` may choose, by size: ``TUNING.quant_auto_formats``
+    (a comma list of ``mxfp4``, ``nvfp4``, ``mxfp6``, ``mx``; default all four),
+    or the third field of ``FP8_FORMAT=auto:0.05:mxfp4,mxfp6,mx``.  The measure
+    is a tensor-wide L2, in which the small blocks that ``nvfp4`` flushes to
+    zero hardly show: leave ``nvfp4`` out for states whose magnitudes differ
+    by tens of octaves between rows."""
+    fields = _fp8_format_fields()
+    raw = fields[2] if fields[0] == "auto" and len(fields) > 2 else ""
+    want = {p.strip().lower() for p in (raw or str(_tuned("quant_auto_formats"))).split(",")}
+    return tuple(f for f in AUTO_FORMATS if f in want) or AUTO_FORMATS
 
 
 def plan_settings() -> tuple:
@@ -635,7 +683,8 @@ def plan_settings() -> tuple:
             get_slab_size_threshold_bytes(), is_batching_disabled(), get_compression(),
             checksum_enabled(), async_hbm_staging_enabled(), hbm_staging_reserve_bytes(),
             hbm_staging_max_bytes(), native_drain_enabled(), native_restore_enabled(),
-            use_direct_io(), fp8_format(), tuple(sorted(vars(TUNING).items())))
+            use_direct_io(), fp8_format(), quant_max_error(), quant_auto_formats(),
+            tuple(sorted(vars(TUNING).items())))
 
 
 @contextmanager

@@ -274,6 +274,8 @@ HSGPU_ABI = {
                                    c_void_p]),
     "hsg_nvfp4_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                      c_void_p]),
+    "hsg_quant_probe_out_bytes": (c_uint64, []),
+    "hsg_quant_probe": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
                                    c_int, c_int, c_int, c_int, P(c_int)]),
     "hsg_drain_wait": (c_int, [c_void_p, P(c_uint64), P(c_uint64), c_char_p, P(c_double)]),
@@ -983,6 +985,39 @@ def nvfp4_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, amax: torc
     _check(lib.hsg_nvfp4_dequantize(dev, q.data_ptr(), scales.data_ptr(), amax.data_ptr(), n,
                                     dst.data_ptr(), dtype_code(dst.dtype), stream_handle),
            "hsg_nvfp4_dequantize")
+
+
+PROBE_FORMATS = ("mxfp4", "nvfp4", "mxfp6", "mx")  # bit i of the mask, column i of the report
+PROBE_REPORT_WORDS = 11  # sumsq, err2[4] (f64), n_finite, spoiled[4] (u64), amax (f32, low half)
+
+
+def quant_probe_workgroup_elems(dtype: torch.dtype) -> int:
+    """Elements one workgroup of hs_quant_probe takes per step: 4 waves of 64
+    lanes x 16 B x 4 in flight (csrc/hsquant.hip kStreamU)."""
+    return 4 * 64 * 4 * (16 // torch.empty(0, dtype=dtype).element_size())
+
+
+def quant_probe_buffer(device) -> torch.Tensor:
+    """The ``out`` of ``quant_probe``: the report's words, then the scratch
+    rows of the workgroups."""
+    return torch.empty(require_gpu_lib().hsg_quant_probe_out_bytes() // 8, dtype=torch.int64,
+                       device=device)
+
+
+def quant_probe(dev: int, src: torch.Tensor, candidates_mask: int, out: torch.Tensor,
+                stream_handle: int) -> None:
+    """Format probe (hs_nvfp4_amax when bit 1 is set, hs_quant_probe,
+    hs_quant_probe_sum): the first ``PROBE_REPORT_WORDS`` words of ``out``
+    (``quant_probe_buffer``) get the sums of ops/quant.py
+    ``format_errors_reference`` for the formats of ``candidates_mask`` (bit i:
+    ``PROBE_FORMATS[i]``).  Nothing is copied to the host or waited for."""
+    lib = require_gpu_lib()
+    assert src.is_contiguous() and dtype_code(src.dtype) in (10, 11, 12)
+    assert out.dtype == torch.int64 and out.is_contiguous()
+    assert out.numel() * 8 >= lib.hsg_quant_probe_out_bytes()
+    _check(lib.hsg_quant_probe(dev, src.data_ptr(), dtype_code(src.dtype), src.numel(),
+                               candidates_mask, out.data_ptr(), stream_handle),
+           "hsg_quant_probe")
 
 
 def mxfp4_hadamard_tiles(dtype: torch.dtype, restore: bool = False) -> int:

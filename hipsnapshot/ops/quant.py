@@ -247,6 +247,26 @@ Relative L2 error of a float64 model of the rules on 2^20 seeded values,
 ``mxfp4`` / ``mxfp4_hadamard32`` / ``nvfp4``: N(0, 1) 0.1154 / 0.1184 / 0.0950;
 Student-t(2) 0.1327 / 0.1011 / 0.0645; Laplace 0.1321 / 0.1151 / 0.0927: 18 to
 50 % less error than ``mxfp4`` for 6 % more bytes.
+
+Error-budgeted choice (opt-in, ``HIPSNAPSHOT_FP8_FORMAT=auto[:max_error[:formats]]``):
+the figures above come from synthetic data, and one format per process is
+wrong for a real state.  ``format_errors(t)`` measures what ``mxfp4`` (4.25
+bits per element), ``nvfp4`` (4.5), ``mxfp6`` (6.25) and ``mx`` (8.25) would
+lose on ``t`` itself -- the sums that ``format_errors_reference`` states, by
+``hs_quant_probe`` in one read of a tensor in HBM (every element round-tripped
+through the four formats in registers, f64 sums reduced in a fixed order, so
+the report is a function of the tensor's bytes) -- and ``choose_format`` picks
+the smallest candidate that spoils no finite element and whose relative L2
+error is within ``knobs.quant_max_error()`` (default 0.03).  A take under
+``auto`` does that for every tensor it writes (``io/tensor.py``), records the
+measured ``rel_l2`` and ``"selected": "auto"`` in the entry's ``quant`` dict,
+and writes a tensor that no candidate serves unquantized.  The rotated formats
+and ``block`` are not candidates.  On an MI355X the probe of 512 Mi bf16
+elements takes 0.99 ms with the amax pass of ``nvfp4`` and 0.66 ms without
+``nvfp4`` among the candidates (f32: 1.35 / 0.79 ms), against 0.39 ms for an
+``nvfp4`` quantization: it is bound by the vector ALU, not by HBM
+(``docs/architecture.md`` section 4); a take of 300 tensors pays about 50 us
+per tensor for it and its host wait.
 """
 
 from __future__ import annotations
@@ -340,36 +360,40 @@ def _round_up(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
-def fp8_entry_quant_info(t: torch.Tensor, vpt: int = DEFAULT_VPT,
-                         rotation: str = None) -> Dict[str, Any]:
-    from .. import knobs
+def fp8_entry_quant_info(t: torch.Tensor, vpt: int = DEFAULT_VPT, rotation: str = None,
+                         fmt: str = None) -> Dict[str, Any]:
+    """The ``quant`` dict of ``t`` under format ``fmt`` (a value of
+    ``knobs.fp8_format()``, which is the default)."""
+    if fmt is None:
+        from .. import knobs
 
+        fmt = knobs.fp8_format()
     n = t.numel()
-    if rotation in (None, "hadamard32") and knobs.fp8_format() == "mxfp4_hadamard32":
+    if rotation in (None, "hadamard32") and fmt == "mxfp4_hadamard32":
         nblocks = _round_up(n, GROUP) // GROUP  # block = rotated group
         return {"format": "fp4_e2m1_mx", "block": MX_BLOCK, "scale": "e8m0",
                 "rotation": "hadamard32", "orig_dtype": dtype_to_string(t.dtype),
                 "payload_bytes": 16 * nblocks, "nblocks": nblocks, "total_bytes": 17 * nblocks}
-    rotation = rotation or default_rotation()
-    if rotation == "none" and knobs.fp8_format() == "mxfp4":
+    rotation = rotation or ("hadamard32" if fmt == "hadamard32" else "none")
+    if rotation == "none" and fmt == "mxfp4":
         payload = mxfp4_payload_bytes(n)
         nblocks = (n + MX_BLOCK - 1) // MX_BLOCK
         return {"format": "fp4_e2m1_mx", "block": MX_BLOCK, "scale": "e8m0",
                 "rotation": "none", "orig_dtype": dtype_to_string(t.dtype),
                 "payload_bytes": payload, "nblocks": nblocks, "total_bytes": payload + nblocks}
-    if rotation == "none" and knobs.fp8_format() == "mxfp6":
+    if rotation == "none" and fmt == "mxfp6":
         payload = mxfp6_payload_bytes(n)
         nblocks = (n + MX_BLOCK - 1) // MX_BLOCK
         return {"format": "fp6_e2m3_mx", "block": MX_BLOCK, "scale": "e8m0",
                 "rotation": "none", "orig_dtype": dtype_to_string(t.dtype), "nblocks": nblocks,
                 "payload_bytes": payload, "total_bytes": payload + nblocks}
-    if rotation == "none" and knobs.fp8_format() == "nvfp4":
+    if rotation == "none" and fmt == "nvfp4":
         payload = nvfp4_payload_bytes(n)
         nblocks = (n + NV_BLOCK - 1) // NV_BLOCK
         return {"format": "fp4_e2m1_nv", "block": NV_BLOCK, "scale": "e4m3+fp32",
                 "rotation": "none", "orig_dtype": dtype_to_string(t.dtype), "nblocks": nblocks,
                 "payload_bytes": payload, "total_bytes": payload + _round_up(nblocks, 4) + 4}
-    if rotation == "none" and default_scale() == "e8m0":
+    if rotation == "none" and fmt != "block":
         payload = _round_up(n, 16)
         nblocks = (n + MX_BLOCK - 1) // MX_BLOCK
         return {"format": "fp8_e4m3fn_mx", "block": MX_BLOCK, "scale": "e8m0",
@@ -665,6 +689,128 @@ def mxfp6_dequantize_reference(payload: torch.Tensor, sbytes: torch.Tensor, n: i
     view, bits = _QUIET_NAN_BITS[dtype]
     out.view(view)[is_nan.repeat_interleave(MX_BLOCK)[:n]] = bits
     return out
+
+
+# ---------------------------------------------------------------------------
+# error-budgeted choice of a format (``HIPSNAPSHOT_FP8_FORMAT=auto``)
+# ---------------------------------------------------------------------------
+
+# the candidates by size: (knob value, bits per element)
+AUTO_FORMATS = (("mxfp4", 4.25), ("nvfp4", 4.5), ("mxfp6", 6.25), ("mx", 8.25))
+
+
+def _restore_f32(flat: torch.Tensor, fmt: str) -> torch.Tensor:
+    n = flat.numel()
+    if fmt == "mxfp4":
+        return mxfp4_dequantize_reference(*mxfp4_quantize_reference(flat), n, torch.float32)
+    if fmt == "nvfp4":
+        payload, sbytes, amax = nvfp4_quantize_reference(flat)
+        return nvfp4_dequantize_reference(payload, sbytes, amax, n, torch.float32)
+    if fmt == "mxfp6":
+        return mxfp6_dequantize_reference(*mxfp6_quantize_reference(flat), n, torch.float32)
+    if fmt == "mx":
+        return mx_dequantize_reference(*mx_quantize_reference(flat), torch.float32)
+    raise ValueError(f"{fmt!r} is not a candidate of the format probe")
+
+
+def _candidates(candidates) -> tuple:
+    names = tuple(name for name, _ in AUTO_FORMATS)
+    if candidates is None:
+        return names
+    unknown = [c for c in candidates if c not in names]
+    if unknown:
+        raise ValueError(f"not candidates of the format probe: {unknown}")
+    return tuple(name for name in names if name in candidates)
+
+
+def _report(n: int, n_finite: int, sumsq: float, per_format: Dict[str, Any]) -> Dict[str, Any]:
+    for f in per_format.values():
+        f["rel"] = (f["err2"] / sumsq) ** 0.5 if sumsq > 0 else 0.0
+    return {"n": n, "n_finite": n_finite, "sumsq": sumsq, "formats": per_format}
+
+
+def format_errors_reference(x: torch.Tensor, candidates=None) -> Dict[str, Any]:
+    """What each candidate format would lose on ``x`` (bf16, f16 or f32), from
+    the references above with the differences and sums in float64.  With
+    ``r_F`` the restore of the flat ``x`` under format ``F`` into fp32
+    (``*_quantize_reference`` then ``*_dequantize_reference(..., float32)``)::
+
+        {"n": n, "n_finite": ..., "sumsq": sum of x_i^2 over the finite x_i,
+         "formats": {F: {"err2": sum of (x_i - r_F,i)^2 over the i where x_i and
+                                 r_F,i are both finite,
+                         "spoiled": number of i where x_i is finite and r_F,i is
+                                    not (the finite neighbours of a NaN in a NaN
+                                    block; the fp32-overflow edge of a code that
+                                    rounds up),
+                         "rel": sqrt(err2 / sumsq), 0 when sumsq == 0}}}
+
+    An inf in ``x`` takes no part in any sum.  ``hs_quant_probe``
+    (``csrc/hsquant.hip``) computes the same numbers in one read of a tensor in
+    HBM; ``format_errors`` dispatches between the two."""
+    flat = x.detach().reshape(-1)
+    xd = flat.double()
+    finite = torch.isfinite(xd)
+    sumsq = float((torch.where(finite, xd, torch.zeros_like(xd)) ** 2).sum())
+    per_format = {}
+    for fmt in _candidates(candidates):
+        r = _restore_f32(flat, fmt).double()
+        both = finite & torch.isfinite(r)
+        err = torch.where(both, xd - r, torch.zeros_like(xd))
+        per_format[fmt] = {"err2": float((err ** 2).sum()),
+                           "spoiled": int((finite & ~torch.isfinite(r)).sum())}
+    return _report(flat.numel(), int(finite.sum()), sumsq, per_format)
+
+
+def format_errors(t: torch.Tensor, candidates=None) -> Dict[str, Any]:
+    """``format_errors_reference``'s report of ``t``: by ``hs_quant_probe`` for a
+    tensor on the GPU (one read, on the current stream, then one host wait for
+    88 bytes), by the reference for a host tensor.  The GPU report is a
+    function of the tensor's bytes: the same on every rank and in every run."""
+    names = _candidates(candidates)
+    if not t.is_cuda:
+        return format_errors_reference(t, names)
+    from . import native
+
+    src = t.detach()
+    src = src if src.is_contiguous() else src.contiguous()
+    mask = sum(1 << native.PROBE_FORMATS.index(name) for name in names)
+    out = native.quant_probe_buffer(t.device)
+    native.quant_probe(t.device.index or 0, src, mask, out,
+                       int(torch.cuda.current_stream(t.device).cuda_stream))
+    words = out[: native.PROBE_REPORT_WORDS].cpu()  # waits for the probe
+    sums, counts = words[:5].view(torch.float64).tolist(), words[5:10].tolist()
+    per_format = {name: {"err2": sums[1 + i], "spoiled": counts[1 + i]}
+                  for i, name in enumerate(native.PROBE_FORMATS) if name in names}
+    return _report(src.numel(), counts[0], sums[0], per_format)
+
+
+def choose_format(report: Dict[str, Any], max_error: float, candidates=None):
+    """The candidate with the fewest bits per element that spoils nothing
+    (``spoiled == 0``) and whose ``rel`` is at most ``max_error``; ``None`` if
+    there is none.  ``report`` is a ``format_errors`` result.
+
+    The measure is a tensor-wide L2 error.  What is small beside the tensor's
+    norm hardly shows in it: the blocks that ``nvfp4`` flushes to zero because
+    they lie 2^22 below the tensor's amax -- whole rows of Adam second moments
+    -- contribute only their own, tiny, squares.  That is why the candidate
+    list is a knob (``knobs.quant_auto_formats``): leave ``nvfp4`` out for such
+    states."""
+    for name in _candidates(candidates):
+        f = report["formats"].get(name)
+        if f is not None and f["spoiled"] == 0 and f["rel"] <= max_error:
+            return name
+    return None
+
+
+def auto_format(t: torch.Tensor):
+    """``(format, measured rel)`` of ``t`` under the ``auto`` knobs, ``(None,
+    None)`` when no candidate is within the budget."""
+    from .. import knobs
+
+    names = knobs.quant_auto_formats()
+    report = format_errors(t, names)
+    fmt = choose_format(report, knobs.quant_max_error(), names)
+    return (fmt, report["formats"][fmt]["rel"]) if fmt is not None else (None, None)
 
 
 def hadamard_matrix(n: int = GROUP, device=None) -> torch.Tensor:

@@ -739,8 +739,11 @@ class Snapshot:
         plan = cache_key = None
         resident: Dict[str, Any] = {}
         # (never for a take with content digests or a base: cached entries and
-        # their JSON must not carry locations rewritten into a base)
-        if not rep_paths and prepare_func is None and incr is None and plan_cache.enabled():
+        # their JSON must not carry locations rewritten into a base; nor for an
+        # ``auto`` quantized take, whose entries depend on the tensors' contents)
+        auto_quant = bool(quantize) and knobs.fp8_format() == "auto"
+        if not rep_paths and prepare_func is None and incr is None and not auto_quant \
+                and plan_cache.enabled():
             with timeline.span("plan_lookup"):
                 resident = {k: v for k, v in flattened.items() if plan_cache.is_resident(v)}
                 if resident:

@@ -4,7 +4,10 @@ for rocprofv3 --stats / --pmc passes): MX (E8M0 per 32), fp32 scale per 128,
 MFMA Hadamard-32, MXFP4 (e2m1 nibbles, E8M0 per 32), Hadamard-rotated MXFP4,
 MXFP6 (e2m3 codes, E8M0 per 32), two-level-scaled FP4 (e2m1 nibbles, e4m3 per
 16 under one fp32 scale; its quantize is three launches and reads the source
-twice, and ``traffic_bytes`` counts that).
+twice, and ``traffic_bytes`` counts that), and the format probe of
+``HIPSNAPSHOT_FP8_FORMAT=auto`` (``probe``: amax + probe + row sum, all four
+candidates, the source read twice and nothing stored; ``probe_mx``: without the
+two-level candidate, one read).
 Prints one JSON line per
 kernel with host-timed GB/s of HBM traffic (read + written bytes), the time
 between device events around the call, and GB/s of the tensor alone (source
@@ -13,7 +16,7 @@ bytes of a quantize, destination bytes of a dequantize).
     fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [--mi-elems M] [mode ...]
 
 Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``, ``mxfp4_hadamard32``,
-``mxfp6``, ``nvfp4``.  ``--rounds R`` goes
+``mxfp6``, ``nvfp4``, ``probe``, ``probe_mx``.  ``--rounds R`` goes
 through the list of modes R times, so that two modes alternate and the spread
 of one mode's repeats is seen beside the difference between the two.
 
@@ -67,6 +70,21 @@ def main():
     w = torch.empty(nw + off, dtype=dtype, device="cuda:0").normal_()[off:]
     hs = int(torch.cuda.current_stream().cuda_stream)
     for mode in modes:
+        if mode in ("probe", "probe_mx"):
+            out = native.quant_probe_buffer(w.device)
+            mask = 15 if mode == "probe" else 13
+            reads = 2 if mode == "probe" else 1
+            best, med, ev_best, ev_med = timeit(lambda: native.quant_probe(dev, w, mask, out, hs))
+            tensor = nw * w.element_size()
+            print(json.dumps({"kernel": mode, "ms_best": round(best * 1e3, 4),
+                              "TBps_best": round(reads * tensor / best / 1e12, 3),
+                              "TBps_median": round(reads * tensor / med / 1e12, 3),
+                              "traffic_bytes": reads * tensor, "elems": nw,
+                              "event_ms_best": round(ev_best * 1e3, 4),
+                              "event_ms_median": round(ev_med * 1e3, 4),
+                              "tensor_GBps_event_median": round(tensor / ev_med / 1e9, 1)}),
+                  flush=True)
+            continue
         if mode == "mx_e8m0":
             info = quant.fp8_entry_quant_info(w, rotation="none")
         elif mode in ("mxfp4", "mxfp4_hadamard32", "mxfp6", "nvfp4"):
