@@ -111,6 +111,11 @@ int hsg_nvfp4_quantize(int dev, const void* src, int src_dtype, int64_t n, void*
                        void* scales, void* amax, void* stream);
 int hsg_nvfp4_dequantize(int dev, const void* q, const void* scales, const void* amax, int64_t n,
                          void* dst, int dst_dtype, void* stream);
+uint64_t hsg_dequant_region_size();
+uint64_t hsg_dequant_regions_workspace_bytes(const void* regions, int nregions, int64_t n);
+int hsg_dequant_regions(int dev, int format, const void* q, const void* scales, const void* amax,
+                        int64_t n, const void* regions, int nregions, void* workspace,
+                        uint64_t ws_bytes, void* pinned_stage, void* stream, int sync);
 uint64_t hsg_quant_probe_out_bytes();
 int hsg_quant_probe(int dev, const void* src, int src_dtype, int64_t n, int candidates_mask,
                     void* out, void* stream);

@@ -11,7 +11,9 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
+#include <vector>
 
 #include "hsgpu_common.h"
 
@@ -442,6 +444,12 @@ hs_fp8_dequant_v(const uint8_t* __restrict__ q, const float* __restrict__ scales
 constexpr uint32_t kFp4NanKey = 0xffffffffu;
 constexpr uint32_t kE8m0Nan = 0xffu;
 
+// a decoded code q under the E8M0 byte sb (MXFP4, MXFP6): q * 2^k, exact in
+// f32; the NaN byte makes a positive quiet NaN
+__device__ __forceinline__ float e8m0_restore(float q, uint32_t sb) {
+  return sb == kE8m0Nan ? __builtin_nanf("") : ldexpf(q, int(sb) - 127);
+}
+
 typedef unsigned short mx_u16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 mx_bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 mx_f16x2 __attribute__((ext_vector_type(2)));
@@ -722,11 +730,9 @@ hs_mxfp4_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scal
         p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 2);
         p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 3);
       }
-      const int k = int(sc[u]) - 127;
       float f[EPL];
 #pragma unroll
-      for (int j = 0; j < EPL; ++j)
-        f[j] = sc[u] == kE8m0Nan ? __builtin_nanf("") : ldexpf(p[j >> 1][j & 1], k);
+      for (int j = 0; j < EPL; ++j) f[j] = e8m0_restore(p[j >> 1][j & 1], sc[u]);
       if (full) {
         fp4_store16<DT>(dst + e0 * DES, f);
       } else {
@@ -794,6 +800,15 @@ constexpr uint32_t kE4m3Nan = 0x7fu;
 
 __device__ __forceinline__ float nvfp4_tensor_scale(float amax) {
   return fmaxf(amax / kNvfp4Top, kNvfp4MinTs);
+}
+
+// a decoded code q under block scale byte s8 and tensor scale ts: q * d with
+// d = f32(s8) * ts (signed zero when s8 == 0); the byte of a NaN block makes a
+// positive quiet NaN
+__device__ __forceinline__ float nvfp4_restore(float q, uint32_t s8, float ts) {
+  const bool nan = (s8 & 0x7fu) == kE4m3Nan;
+  const float d = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(s8), 0) * ts;
+  return nan ? __builtin_nanf("") : q * d;
 }
 
 // the f32 value of a finite |x| pattern of the source dtype
@@ -997,11 +1012,9 @@ hs_nvfp4_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scal
         p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 2);
         p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw[u], 1.0f, 3);
       }
-      const bool nan = (sc[u] & 0x7fu) == kE4m3Nan;  // the byte of a NaN block
-      const float d = __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(sc[u]), 0) * ts;
       float f[EPL];
 #pragma unroll
-      for (int j = 0; j < EPL; ++j) f[j] = nan ? __builtin_nanf("") : p[j >> 1][j & 1] * d;
+      for (int j = 0; j < EPL; ++j) f[j] = nvfp4_restore(p[j >> 1][j & 1], sc[u], ts);
       if (full) {
         fp4_store16<DT>(dst + e0 * DES, f);
       } else {
@@ -1234,6 +1247,14 @@ hs_mxfp6_quant(const char* __restrict__ src, int64_t n, int64_t payload,
   }
 }
 
+// the f32 values of the 32 codes in six payload dwords, at scale 1
+__device__ __forceinline__ mx_f32x32 fp6_decode32(const uint32_t* c) {
+  const mx_u32x6 cv = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  const mx_f32x32 dec = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(cv, 1.0f);
+  asm volatile("" ::"v"(cv));  // no register shared with dec (see fp6_pack)
+  return dec;
+}
+
 template <int DT>
 __global__ void __launch_bounds__(kBlock)
 hs_mxfp6_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scales, int64_t n,
@@ -1281,13 +1302,10 @@ hs_mxfp6_dequant(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scal
 #pragma unroll
       for (int t = 0; t < 24; ++t) c[t >> 2] |= uint32_t(q[24 * blk + t]) << (8 * (t & 3));
     }
-    const mx_u32x6 cv = {c[0], c[1], c[2], c[3], c[4], c[5]};
-    const mx_f32x32 dec = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(cv, 1.0f);
-    asm volatile("" ::"v"(cv));  // no register shared with dec (see fp6_pack)
-    const int k = int(sb) - 127;
+    const mx_f32x32 dec = fp6_decode32(c);
     float f[32];
 #pragma unroll
-    for (int j = 0; j < 32; ++j) f[j] = sb == kE8m0Nan ? __builtin_nanf("") : ldexpf(dec[j], k);
+    for (int j = 0; j < 32; ++j) f[j] = e8m0_restore(dec[j], sb);
     if (full) {
 #pragma unroll
       for (int h = 0; h < PASSES; ++h) {
@@ -2271,6 +2289,271 @@ hs_quant_probe_sum(const uint64_t* __restrict__ rows, int nrows, uint64_t* __res
 }
 
 // ---------------------------------------------------------------------------
+// Region-scatter dequantizer (hs_dequant_regions): one launch decodes any
+// number of N-d boxes of ONE quantized piece in HBM into strided destinations
+// (the restore of a quantized FSDP / DTensor shard into another layout, and of
+// a quantized tensor into a non-contiguous view).  Formats: MX fp8, MXFP4
+// without rotation, MXFP6 and the two-level-scaled FP4 -- the ones whose
+// element i is decodable on its own, its code and its scale byte at offsets
+// computed from i.  The rotated formats need whole groups of 32 through the
+// matrix cores and keep their kernels; so does the f32-scale block layout.
+// The rules are the streaming kernels': the same device functions decode
+// (fp8_byte_to_f32 + MxScale::restore, v_cvt_scalef32_pk_f32_fp4 +
+// e8m0_restore / nvfp4_restore, fp6_decode32 + e8m0_restore) and round
+// (pack16 / store_from_f32), so a region equals the whole piece's restore,
+// narrowed, bit for bit.  One thing is stated here and nowhere else, and it is
+// no rule of the format: the region restore is held to the bits of the torch
+// CPU reference (ops/quant.py
+// mx_dequantize_reference) also for the e4m3fn NaN codes of MX fp8 (a stored
+// inf / NaN): torch widens the code 0x7F / 0xFF to the f32 sign | 0x7FF00000,
+// which an f16 destination truncates to sign | 0x7F80 and which torch's
+// vector f32 -> bf16 turns into 0xFFFF whatever the sign (qnan_store).
+// hs_mx8_dequant leaves such an element as the NaN of v_cvt_f32_fp8 and of
+// the destination's rounding, as it always did.
+//
+// Host: a region arrives with its dims collapsed against the piece's C order
+// and the destination's strides (ops/native.py), innermost dim a run of
+// consecutive source elements.  build_qtiles cuts every region into tiles
+// {region, begin, end} in region-linear elements: whole runs where a run is
+// shorter than a tile, else pieces of one run cut where the SOURCE index is a
+// multiple of 32, so that no block, byte or 3-byte group is shared by two
+// tiles' full groups.  Descriptors and tiles go up through a pinned stage into
+// a device workspace, as in hsg_copy_nd.
+//
+// Device: workgroups of 256 walk the tile table.  The unit is an aligned group
+// of 8 consecutive source elements -- 8 B of fp8, 4 B of fp4, 6 B of fp6; 8
+// divides 16 and 32, so a group has one scale byte, loaded once.  A tile of R
+// runs has R * G slots, G the largest number of groups a run of that length
+// can touch; slot w is group w % G of run w / G (a 32-bit division), so
+// adjacent lanes own adjacent groups of a run and a wave's payload loads are
+// contiguous; a run that touches fewer groups leaves its last slot idle.  The
+// run's outer coordinates cost one 64-bit division per outer dim but the first,
+// per group.  The first and the last group of a run are masked per element.
+// When the destination's innermost stride is 1, the group is whole and its
+// address is 16-B aligned, it leaves as one nontemporal 16-B store (bf16 /
+// f16) or two (f32); otherwise element by element.  The 6-bit codes of a group
+// come out of two aligned dwords by a shift (a group starts 6 g bytes into the
+// payload: 0 or 2 past a dword) and go through the block conversion with the
+// other 24 codes zero.  No LDS.  A and ts of the two-level format are formed
+// once, before the tile loop.
+// ---------------------------------------------------------------------------
+
+constexpr int kQMaxDims = 8;
+
+enum QFormat : int32_t { kQMx8 = 0, kQMxfp4 = 1, kQMxfp6 = 2, kQNvfp4 = 3, kQFormats = 4 };
+
+struct QRegion {
+  char* dst;        // destination of the region's first element
+  int64_t src0;     // piece-linear index of the region's first element
+  int64_t numel;
+  int32_t ndim;     // collapsed dims; the last one is a run of the source
+  int32_t dst_dtype;
+  int64_t sizes[kQMaxDims];
+  int64_t src_strides[kQMaxDims];  // in elements of the piece
+  int64_t dst_strides[kQMaxDims];  // in elements
+};
+
+struct QTile {
+  int32_t region;
+  int32_t pad;
+  int64_t begin;  // region-linear elements
+  int64_t end;
+};
+
+constexpr int64_t kQTileElems = 8192;  // smallest tile: 4 groups per lane (ops/native.py)
+
+// an e4m3fn NaN code with sign bit `neg`, as the torch reference restores it
+template <int DT>
+__device__ __forceinline__ void qnan_store(char* p, uint32_t neg) {
+  if constexpr (DT == kF32) *reinterpret_cast<uint32_t*>(p) = (neg << 31) | 0x7ff00000u;
+  else if constexpr (DT == kF16) *reinterpret_cast<uint16_t*>(p) = uint16_t((neg << 15) | 0x7f80u);
+  else *reinterpret_cast<uint16_t*>(p) = 0xffffu;
+}
+
+// the 8 decoded f32 values of the group at source element gs (a multiple of
+// 8); MX fp8: bit j of `nan` for an e4m3fn NaN code, bit 8 + j its sign
+template <int F>
+__device__ __forceinline__ void qgroup_decode(const uint8_t* __restrict__ q,
+                                              const uint8_t* __restrict__ scales, float ts,
+                                              int64_t gs, float* f, uint32_t& nan) {
+  nan = 0;
+  if constexpr (F == kQMx8) {
+    const uint2 w = *reinterpret_cast<const uint2*>(q + gs);
+    const uint8_t sb = scales[gs >> 5];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      f[j] = MxScale::restore(fp8_byte_to_f32(j < 4 ? w.x : w.y, j & 3), sb);
+      const uint32_t code = ((j < 4 ? w.x : w.y) >> (8 * (j & 3))) & 0xffu;
+      if ((code & 0x7fu) == 0x7fu) nan |= (1u << j) | ((code >> 7) << (8 + j));
+    }
+  } else if constexpr (F == kQMxfp6) {
+    // 6 bytes at 6 * (gs / 8): the two dwords around them, shifted
+    const int64_t at = (gs >> 3) * 6;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(q + (at & ~int64_t(3)));
+    const uint64_t bits = ((uint64_t(w[1]) << 32) | w[0]) >> (8 * int(at & 3));
+    const uint32_t c[6] = {uint32_t(bits), uint32_t(bits >> 32) & 0xffffu, 0, 0, 0, 0};
+    const mx_f32x32 dec = fp6_decode32(c);
+    const uint32_t sb = scales[gs >> 5];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = e8m0_restore(dec[j], sb);
+  } else {
+    const uint32_t raw = *reinterpret_cast<const uint32_t*>(q + (gs >> 1));
+    mx_f32x2 p[4];  // the byte select must be an immediate
+    p[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 0);
+    p[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 1);
+    p[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 2);
+    p[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 3);
+    const uint32_t sb = scales[F == kQNvfp4 ? gs >> 4 : gs >> 5];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      f[j] = F == kQNvfp4 ? nvfp4_restore(p[j >> 1][j & 1], sb, ts)
+                          : e8m0_restore(p[j >> 1][j & 1], sb);
+  }
+}
+
+template <int F, int DT>
+__device__ __forceinline__ void qtile(const QRegion& r, int64_t begin, int64_t end,
+                                      const uint8_t* __restrict__ q,
+                                      const uint8_t* __restrict__ scales, float ts) {
+  constexpr int DES = (DT == kF32) ? 4 : 2;
+  const int nd = r.ndim;
+  const int64_t L = r.sizes[nd - 1];
+  const int64_t dinner = r.dst_strides[nd - 1];
+  // whole runs [run0, run0 + nruns) of the region, or [lo, hi) of run run0
+  const int64_t run0 = begin / L;
+  int64_t lo = begin - run0 * L, hi = lo + (end - begin);
+  uint32_t nruns = 1;
+  if (lo == 0 && hi >= L) {
+    nruns = static_cast<uint32_t>(hi / L);
+    hi = L;
+  }
+  const uint32_t G = static_cast<uint32_t>((hi - lo + 6) / 8 + 1);  // groups a run can touch
+  const uint32_t slots = nruns * G;
+  for (uint32_t w = threadIdx.x; w < slots; w += kBlock) {
+    const uint32_t lr = w / G, g = w - lr * G;
+    int64_t rest = run0 + lr, soff = r.src0, doff = 0;
+    for (int k = nd - 2; k >= 0; --k) {
+      int64_t c = rest;
+      if (k > 0) {
+        const int64_t sz = r.sizes[k];
+        rest = rest / sz;
+        c -= rest * sz;
+      }
+      soff += c * r.src_strides[k];
+      doff += c * r.dst_strides[k];
+    }
+    const int64_t S = soff + lo, E = soff + hi;  // the run's source elements
+    const int64_t gs = (S & ~int64_t(7)) + 8 * int64_t(g);
+    if (gs >= E) continue;
+    float f[8];
+    uint32_t nan;
+    qgroup_decode<F>(q, scales, ts, gs, f, nan);
+    char* p = r.dst + (doff + (gs - soff) * dinner) * DES;  // of element gs (maybe masked)
+    if (nan) {  // rare: element stores, the NaN codes by their bits
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (gs + j < S || gs + j >= E) continue;
+        if ((nan >> j) & 1) qnan_store<DT>(p + j * dinner * DES, (nan >> (8 + j)) & 1);
+        else store_from_f32(p + j * dinner * DES, DT, f[j]);
+      }
+    } else if (dinner == 1 && gs >= S && gs + 8 <= E && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+      if constexpr (DT == kF32) {
+        fp4_store16<kF32>(p, f);
+        fp4_store16<kF32>(p + 16, f + 4);
+      } else {
+        fp4_store16<DT>(p, f);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (gs + j >= S && gs + j < E) store_from_f32(p + j * dinner * DES, DT, f[j]);
+    }
+  }
+}
+
+template <int F>
+__global__ void HS_NO_PK_F32 __launch_bounds__(kBlock)
+hs_dequant_regions(const QRegion* __restrict__ regions, const QTile* __restrict__ tiles,
+                   int64_t ntiles, const uint8_t* __restrict__ q,
+                   const uint8_t* __restrict__ scales, const float* __restrict__ amax) {
+  float ts = 0.f;
+  if constexpr (F == kQNvfp4) ts = nvfp4_tensor_scale(*amax);
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const QTile tile = tiles[t];
+    const QRegion& r = regions[tile.region];
+    switch (r.dst_dtype) {
+      case kBF16: qtile<F, kBF16>(r, tile.begin, tile.end, q, scales, ts); break;
+      case kF16: qtile<F, kF16>(r, tile.begin, tile.end, q, scales, ts); break;
+      default: qtile<F, kF32>(r, tile.begin, tile.end, q, scales, ts); break;
+    }
+  }
+}
+
+// The tile table of a validated region batch.  Tiles grow with the batch so
+// that a launch has about 4096 of them when there is that much work.
+void build_qtiles(const QRegion* regions, int n, std::vector<QTile>* tiles) {
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) total += regions[i].numel;
+  const int64_t tile = std::max(kQTileElems, std::min<int64_t>(kQTileElems * 32,
+                                                               total / 4096 / 2048 * 2048));
+  for (int i = 0; i < n; ++i) {
+    const QRegion& r = regions[i];
+    const int64_t L = r.sizes[r.ndim - 1], nruns = r.numel / L;
+    if (L <= tile) {
+      const int64_t per = tile / L;  // whole runs per tile
+      for (int64_t run = 0; run < nruns; run += per)
+        tiles->push_back(QTile{i, 0, run * L, std::min(nruns, run + per) * L});
+      continue;
+    }
+    for (int64_t run = 0; run < nruns; ++run) {
+      int64_t rest = run, s = r.src0;
+      for (int k = r.ndim - 2; k >= 0; --k) {
+        const int64_t c = k > 0 ? rest % r.sizes[k] : rest;
+        rest = k > 0 ? rest / r.sizes[k] : 0;
+        s += c * r.src_strides[k];
+      }
+      // cut where the source index is a multiple of 32 (tile % 32 == 0)
+      for (int64_t b = 0, e = tile - (s & 31); b < L; b = e, e += tile)
+        tiles->push_back(QTile{i, 0, run * L + b, run * L + std::min(e, L)});
+    }
+  }
+}
+
+// 0 if every region lies inside the piece of n elements and is well formed;
+// else the error is set.  Nothing of a rejected batch is read on the device.
+int check_qregions(const QRegion* regions, int nregions, int64_t n) {
+  for (int i = 0; i < nregions; ++i) {
+    const QRegion& r = regions[i];
+    if (r.ndim < 1 || r.ndim > kQMaxDims) {
+      hs_set_error("region %d: %d dims (1 to %d are supported)", i, r.ndim, kQMaxDims);
+      return -1004;
+    }
+    if (r.dst_dtype != kBF16 && r.dst_dtype != kF16 && r.dst_dtype != kF32) {
+      hs_set_error("region %d: unsupported destination dtype %d", i, r.dst_dtype);
+      return -1002;
+    }
+    int64_t numel = 1, last = r.src0;
+    bool ok = r.src0 >= 0 && r.src0 < n && r.dst != nullptr &&
+              r.src_strides[r.ndim - 1] == 1;
+    for (int k = 0; ok && k < r.ndim; ++k) {
+      const int64_t sz = r.sizes[k], st = r.src_strides[k];
+      // by division: no product is formed before it is known to stay below n
+      ok = sz >= 1 && st >= 0 && numel <= n / sz &&
+           (sz == 1 || st == 0 || sz - 1 <= (n - 1 - last) / st);
+      if (!ok) break;
+      numel *= sz;
+      last += (sz - 1) * st;
+    }
+    if (!ok || numel != r.numel) {
+      hs_set_error("region %d reaches outside the piece of %lld elements or is malformed", i,
+                   static_cast<long long>(n));
+      return -1005;
+    }
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Host dispatch: a runtime dtype code or vpt becomes a template argument by
 // calling `f` with an integral_constant of it; kNoKernel where none fits.
 // ---------------------------------------------------------------------------
@@ -2535,6 +2818,85 @@ int hsg_mxfp4_hadamard_dequantize(int dev, const void* q, const void* scales, in
                   scales, n, nblocks, dst);
   });
   return rc == kNoKernel ? unsupported_dtype("mxfp4 hadamard dest", dst_dtype) : rc;
+}
+
+// Region-scatter dequantize (hs_dequant_regions above).  `regions` is a host
+// array of `nregions` QRegion (ops/native.py DEQUANT_REGION_DTYPE) over ONE
+// piece of `n` elements in format `format` (QFormat: 0 MX fp8, 1 MXFP4, 2
+// MXFP6, 3 two-level FP4): `q` its payload (8-byte aligned; whole groups of 8
+// codes are read, so it must be padded as the four layouts pad it, to a
+// multiple of 16 bytes), `scales` its scale bytes, `amax` the f32 of format 3 (4-byte aligned; unused otherwise).
+// `workspace` (device) and `pinned_stage` (host) hold at least
+// hsg_dequant_regions_workspace_bytes() bytes: the tables go up on `stream`, so
+// the host array may be reused when this returns.  A batch with a region that
+// reaches outside the piece, has more than 8 dims or another destination
+// dtype than bf16 / f16 / f32 is refused before anything is launched.
+uint64_t hsg_dequant_region_size() { return sizeof(QRegion); }
+
+// 0 and the error set for a batch that hsg_dequant_regions would refuse
+uint64_t hsg_dequant_regions_workspace_bytes(const void* regions, int nregions, int64_t n) {
+  const QRegion* r = static_cast<const QRegion*>(regions);
+  if (!r) hs_set_error("null region table");
+  if (!r || nregions <= 0 || n <= 0 || check_qregions(r, nregions, n) != 0) return 0;
+  std::vector<QTile> tiles;
+  build_qtiles(r, nregions, &tiles);
+  return sizeof(QRegion) * nregions + sizeof(QTile) * tiles.size() + 256;
+}
+
+int hsg_dequant_regions(int dev, int format, const void* q, const void* scales, const void* amax,
+                        int64_t n, const void* regions, int nregions, void* workspace,
+                        uint64_t ws_bytes, void* pinned_stage, void* stream, int sync) {
+  HS_CHECK(hipSetDevice(dev));
+  if (nregions <= 0) return 0;
+  if (format < 0 || format >= kQFormats) {
+    hs_set_error("unknown quantized format id %d", format);
+    return -1006;
+  }
+  if (!workspace || !pinned_stage || !regions) {
+    hs_set_error("null %s", !regions ? "region table" : workspace ? "pinned stage" : "workspace");
+    return -1007;
+  }
+  if (n <= 0 || !q || !scales || (reinterpret_cast<uintptr_t>(q) & 7)) {
+    hs_set_error("payload %p of %lld elements: null, empty or not 8-byte aligned", q,
+                 static_cast<long long>(n));
+    return -1008;
+  }
+  if (format == kQNvfp4 && (!amax || (reinterpret_cast<uintptr_t>(amax) & 3)))
+    return misaligned_amax(amax);
+  const QRegion* r = static_cast<const QRegion*>(regions);
+  if (const int rc = check_qregions(r, nregions, n)) return rc;
+  std::vector<QTile> tiles;
+  build_qtiles(r, nregions, &tiles);
+  const size_t dbytes = sizeof(QRegion) * nregions;
+  const size_t tbytes = sizeof(QTile) * tiles.size();
+  const size_t toff = (dbytes + 255) / 256 * 256;
+  if (toff + tbytes > ws_bytes) {
+    hs_set_error("workspace too small: need %zu have %llu", toff + tbytes,
+                 static_cast<unsigned long long>(ws_bytes));
+    return -1000;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* stage = static_cast<char*>(pinned_stage);
+  std::memcpy(stage, r, dbytes);
+  std::memcpy(stage + toff, tiles.data(), tbytes);
+  char* ws = static_cast<char*>(workspace);
+  HS_CHECK(hipMemcpyAsync(ws, stage, toff + tbytes, hipMemcpyHostToDevice, s));
+  const int64_t ntiles = static_cast<int64_t>(tiles.size());
+  int grid = static_cast<int>(std::min<int64_t>(ntiles, 256 * 8));
+  const int cap = hsg_thread_grid_cap();
+  if (cap > 0) grid = std::min(grid, cap);
+  const QRegion* dr = reinterpret_cast<const QRegion*>(ws);
+  const QTile* dt = reinterpret_cast<const QTile*>(ws + toff);
+  int rc;
+  switch (format) {
+    case kQMx8: rc = launch(hs_dequant_regions<kQMx8>, grid, stream, dr, dt, ntiles, q, scales, amax); break;
+    case kQMxfp4: rc = launch(hs_dequant_regions<kQMxfp4>, grid, stream, dr, dt, ntiles, q, scales, amax); break;
+    case kQMxfp6: rc = launch(hs_dequant_regions<kQMxfp6>, grid, stream, dr, dt, ntiles, q, scales, amax); break;
+    default: rc = launch(hs_dequant_regions<kQNvfp4>, grid, stream, dr, dt, ntiles, q, scales, amax); break;
+  }
+  if (rc != 0) return rc;
+  if (sync) HS_CHECK(hipStreamSynchronize(s));
+  return 0;
 }
 
 // bytes of the `out` buffer of hsg_quant_probe: the report row, then a row of

@@ -867,6 +867,44 @@ def _scatter_host_regions(host_addr: int, nbytes: int, regions, dev: int,
     timeline.add("h2d_wait", "h2d", t_w, time.perf_counter(), bytes=nbytes)
 
 
+def quant_regions_on_device(entry, dsts) -> bool:
+    """Whether ``dequant_host_regions`` serves a quantized entry restored into
+    the tensors ``dsts``: a region-decodable format, CUDA destinations on one
+    device, of a dtype the decoder writes."""
+    from ..format.serialization import FP8_QUANTIZABLE_DTYPES
+    from ..ops import quant
+
+    return (len(dsts) > 0 and quant.gpu_region_decodable(entry.quant)
+            and all(d.is_cuda and d.dtype in FP8_QUANTIZABLE_DTYPES
+                    and d.dim() <= native.MAX_DIMS for d in dsts)
+            and len({d.device for d in dsts}) == 1)
+
+
+def dequant_host_regions(host_addr: int, entry, regions, dev: int,
+                         producer: Optional[int] = None) -> None:
+    """The quantized blob of ``entry`` at ``host_addr`` (pinned): one H2D of
+    ``quant["total_bytes"]`` into HBM, then ``quant.dequantize_regions`` of
+    ``regions`` ((narrows or None, dst_view)) on the copy stream, which is
+    ordered after ``producer`` and synchronized before this returns (the host
+    buffer can go back)."""
+    from ..ops import quant
+
+    total = entry.quant["total_bytes"]
+    with timeline.span("h2d_dequant", "h2d", bytes=total, regions=len(regions)):
+        slot = copy_slot()
+        # order after pending work on the destinations' stream (captured at plan time)
+        native.memcpy(dev, slot, 0, 0, 0, native.H2D, producer, sync=False)
+        blob = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+        _join_current_stream(dev, slot)
+        native.memcpy(dev, slot, blob.data_ptr(), host_addr, total, native.H2D, None, sync=False)
+        keep = quant.dequantize_regions(blob, entry, regions, native.copy_stream(dev, slot))
+        try:
+            native.stream_sync(dev, slot)
+        finally:
+            if keep is not None:
+                keep[0].release()
+
+
 # below this, one hipMemcpyAsync is cheaper than an uncached block + a kernel
 _SDMA_MIN_BYTES = 1 << 20
 

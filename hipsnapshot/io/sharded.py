@@ -472,7 +472,12 @@ class ShardedTensorBufferConsumer(BufferConsumer):
         self._gpu = (entry.serializer == SER.BUFFER_PROTOCOL
                      and all(r.dst.is_cuda for r in regions) and len(regions) > 0
                      and len({r.dst.device for r in regions}) == 1)
-        self.producer = staging.producer_stream_handle(regions[0].dst) if self._gpu else None
+        # a quantized shard in a region-decodable format: decoded on the GPU,
+        # region by region (staging.dequant_host_regions)
+        self._quant_gpu = (entry.serializer == SER.FP8_BLOCK
+                           and staging.quant_regions_on_device(entry, [r.dst for r in regions]))
+        self.producer = (staging.producer_stream_handle(regions[0].dst)
+                         if self._gpu or self._quant_gpu else None)
         self._direct = False
 
     def _whole_piece_dst(self, nbytes: int) -> Optional[torch.Tensor]:
@@ -496,10 +501,10 @@ class ShardedTensorBufferConsumer(BufferConsumer):
             # UVM table pages in host DRAM: read the file straight into them
             self._direct = True
             return staging.managed_host_view(dst, self.producer)
-        return self._pinned_dest(nbytes)
+        return self._pinned_dest(nbytes, self._gpu or self._quant_gpu)
 
-    def _pinned_dest(self, nbytes: int) -> Optional[StagedBuffer]:
-        if self._gpu:
+    def _pinned_dest(self, nbytes: int, wanted: bool) -> Optional[StagedBuffer]:
+        if wanted:
             from ..ops import native
 
             pb = native.PinnedBuffer(nbytes)
@@ -508,7 +513,7 @@ class ShardedTensorBufferConsumer(BufferConsumer):
 
     def get_compressed_read_dest(self, nbytes: int) -> Optional[StagedBuffer]:
         # encoded bytes are never the destination's bytes: no direct read
-        return self._pinned_dest(nbytes)
+        return self._pinned_dest(nbytes, self._gpu)
 
     async def consume_buffer(self, buf, executor: Optional[Executor] = None) -> None:
         if self._direct:
@@ -530,6 +535,12 @@ class ShardedTensorBufferConsumer(BufferConsumer):
                         _narrow_dst(r.dst, r.narrows)) for r in self.regions]
             staging.scatter_host_regions(staging.host_buffer_addr(buf),
                                          tensor_nbytes_from_entry(self.entry), regions,
+                                         staging.device_of(self.regions[0].dst), self.producer)
+            return
+        if self._quant_gpu and isinstance(buf, StagedBuffer):
+            regions = [([(d, so, ln) for d, so, _do, ln in r.narrows],
+                        _narrow_dst(r.dst, r.narrows)) for r in self.regions]
+            staging.dequant_host_regions(buf.addr, self.entry, regions,
                                          staging.device_of(self.regions[0].dst), self.producer)
             return
         src = deserialize_tensor(buf, self.entry)

@@ -344,8 +344,19 @@ class TensorBufferConsumer(BufferConsumer):
         return (t is not None and t.is_cuda and self.entry.serializer == SER.FP8_BLOCK
                 and t.is_contiguous() and t.dtype == string_to_dtype(self.entry.dtype))
 
+    def _fp8_regions_on_device(self) -> bool:
+        """A quantized tensor into a CUDA destination that ``_fp8_on_device``
+        does not take because it is not contiguous: one whole-piece region
+        through the region dequantizer.  Another dtype than the entry's keeps
+        the host path (round to the entry's dtype, then cast)."""
+        t = self.tensor
+        return (t is not None and self.entry.serializer == SER.FP8_BLOCK
+                and list(t.shape) == list(self.entry.shape)
+                and t.dtype == string_to_dtype(self.entry.dtype)
+                and staging.quant_regions_on_device(self.entry, [t]))
+
     def get_read_dest(self, nbytes: int) -> Optional[StagedBuffer]:
-        if self._fp8_on_device():
+        if self._fp8_on_device() or self._fp8_regions_on_device():
             from ..ops import native
 
             pb = native.PinnedBuffer(nbytes)
@@ -412,6 +423,10 @@ class TensorBufferConsumer(BufferConsumer):
                           int(torch.cuda.current_stream(t.device).cuda_stream), sync=True)
             dequantize_device(blob, self.entry, t)
             torch.cuda.current_stream(t.device).synchronize()
+            return
+        if self._fp8_regions_on_device() and isinstance(buf, StagedBuffer):
+            staging.dequant_host_regions(buf.addr, self.entry, [(None, t)], staging.device_of(t),
+                                         self.producer)
             return
         if (t.is_cuda and self.entry.serializer == SER.BUFFER_PROTOCOL):
             staging.h2d_into(t, staging.host_buffer_addr(buf), self._nbytes(),

@@ -274,6 +274,10 @@ HSGPU_ABI = {
                                    c_void_p]),
     "hsg_nvfp4_dequantize": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                      c_void_p]),
+    "hsg_dequant_region_size": (c_uint64, []),
+    "hsg_dequant_regions_workspace_bytes": (c_uint64, [c_void_p, c_int, c_int64]),
+    "hsg_dequant_regions": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_int]),
     "hsg_quant_probe_out_bytes": (c_uint64, []),
     "hsg_quant_probe": (c_int, [c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "hsg_drain_start": (c_void_p, [c_int, c_int, P(c_uint64), P(c_uint64), P(c_char_p), c_uint64,
@@ -985,6 +989,104 @@ def nvfp4_dequantize(dev: int, q: torch.Tensor, scales: torch.Tensor, amax: torc
     _check(lib.hsg_nvfp4_dequantize(dev, q.data_ptr(), scales.data_ptr(), amax.data_ptr(), n,
                                     dst.data_ptr(), dtype_code(dst.dtype), stream_handle),
            "hsg_nvfp4_dequantize")
+
+
+# ---- region-scatter dequantize ------------------------------------------------
+
+# `format` of hsg_dequant_regions (csrc/hsquant.hip QFormat), by the entry's
+# ``quant["format"]``; ``fp4_e2m1_mx`` only with rotation ``none``
+DEQUANT_FORMATS = {"fp8_e4m3fn_mx": 0, "fp4_e2m1_mx": 1, "fp6_e2m3_mx": 2, "fp4_e2m1_nv": 3}
+DEQUANT_TILE_ELEMS = 8192  # smallest tile of hs_dequant_regions (kQTileElems)
+DEQUANT_GROUP = 8          # source elements a lane decodes at a time
+DEQUANT_REGION_DTYPE = np.dtype([
+    ("dst", np.uint64), ("src0", np.int64), ("numel", np.int64), ("ndim", np.int32),
+    ("dst_dtype", np.int32), ("sizes", np.int64, (MAX_DIMS,)),
+    ("src_strides", np.int64, (MAX_DIMS,)), ("dst_strides", np.int64, (MAX_DIMS,)),
+])
+
+
+def dequant_region_row(shape: Sequence[int], narrows, dst: torch.Tensor) -> Optional[tuple]:
+    """One region of a piece of C-order ``shape`` as a descriptor row: the box
+    ``narrows`` ((dim, start, length) per narrowed dim, None = the whole piece)
+    goes to ``dst``, a view of the box's shape with any strides.  Dims are
+    collapsed against the piece's C order and ``dst``'s strides; the last
+    collapsed dim is a run of consecutive source elements.  None for an empty
+    region."""
+    shape = [int(z) for z in shape]
+    strides = [1] * len(shape)
+    for i in range(len(shape) - 2, -1, -1):
+        strides[i] = strides[i + 1] * shape[i + 1]
+    sizes, src0 = list(shape), 0
+    for d, start, length in narrows or ():
+        if start < 0 or length < 0 or start + length > shape[d]:
+            raise ValueError(f"region [{start}, {start + length}) of dim {d} reaches outside "
+                             f"the piece of shape {shape}")
+        sizes[d] = int(length)
+        src0 += int(start) * strides[d]
+    if list(dst.shape) != sizes:
+        raise ValueError(f"destination shape {list(dst.shape)} is not the region's {sizes}")
+    if dtype_code(dst.dtype) not in (10, 11, 12):
+        raise ValueError(f"region destination dtype {dst.dtype} unsupported")
+    numel = 1
+    for z in sizes:
+        numel *= z
+    if numel == 0:
+        return None
+    z, a, b = collapse_dims(sizes, strides, dst.stride())
+    if a[-1] != 1:  # a box one element wide: runs of length 1
+        z, a, b = z + [1], a + [1], b + [1]
+    if len(z) > MAX_DIMS:
+        raise ValueError(f"too many non-mergeable dims ({len(z)}) for the region dequantizer")
+    return (dst.data_ptr(), src0, numel, len(z), dtype_code(dst.dtype), z, a, b)
+
+
+def dequant_regions(dev: int, fmt: str, q: torch.Tensor, scales: torch.Tensor,
+                    amax: Optional[torch.Tensor], shape: Sequence[int], regions,
+                    stream_handle: int, sync: bool = True):
+    """Region-scatter dequantize (hs_dequant_regions): ONE launch decodes every
+    ``(narrows or None, dst_view)`` of ``regions`` from the quantized piece of
+    C-order ``shape`` whose payload, scale bytes and (``fp4_e2m1_nv``) amax
+    slot are ``q`` / ``scales`` / ``amax`` in HBM, into CUDA views of bf16, f16
+    or f32 with any strides.  ``fmt`` is a key of ``DEQUANT_FORMATS``.  Like
+    ``launch_packed``: with ``sync=False`` the caller keeps the returned objects
+    until it has synchronized the stream."""
+    lib = require_gpu_lib()
+    if lib.hsg_dequant_region_size() != DEQUANT_REGION_DTYPE.itemsize:
+        raise HipError("QRegion layout mismatch between _hsgpu.so and ops/native.py")
+    rows = [r for r in (dequant_region_row(shape, nar, dst) for nar, dst in regions)
+            if r is not None]
+    if not rows:
+        return None
+    n = 1
+    for z in shape:
+        n *= int(z)
+    arr = np.zeros(len(rows), dtype=DEQUANT_REGION_DTYPE)
+    for i, (dst, src0, numel, nd, dc, z, a, b) in enumerate(rows):
+        arr[i] = (dst, src0, numel, nd, dc, tuple(z) + _ZPAD[nd], tuple(a) + _ZPAD[nd],
+                  tuple(b) + _ZPAD[nd])
+    assert q.dtype == torch.uint8 and scales.dtype == torch.uint8
+    ws_bytes = int(lib.hsg_dequant_regions_workspace_bytes(arr.ctypes.data, len(arr), n))
+    if ws_bytes == 0:
+        _check(-1, "hsg_dequant_regions_workspace_bytes")
+    stage = PinnedBuffer(ws_bytes)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
+    cur = torch.cuda.current_stream(dev)
+    if int(cur.cuda_stream) != int(stream_handle):
+        # the workspace is only safe in the current stream's order (launch_packed)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        torch.cuda.ExternalStream(int(stream_handle), device=f"cuda:{dev}").wait_event(ev)
+    rc = lib.hsg_dequant_regions(dev, DEQUANT_FORMATS[fmt], q.data_ptr(), scales.data_ptr(),
+                                 amax.data_ptr() if amax is not None else None, n,
+                                 arr.ctypes.data, len(arr), ws.data_ptr(), ws_bytes, stage.ptr,
+                                 stream_handle, 1 if sync else 0)
+    if rc != 0:
+        stage.release()
+    _check(rc, "hsg_dequant_regions")
+    if sync:
+        stage.release()
+        return None
+    return (stage, ws)
 
 
 PROBE_FORMATS = ("mxfp4", "nvfp4", "mxfp6", "mx")  # bit i of the mask, column i of the report

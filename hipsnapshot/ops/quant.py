@@ -1072,3 +1072,56 @@ def dequantize_device(blob_dev: torch.Tensor, entry: TensorEntry, dst: torch.Ten
         native.fp8_hadamard_dequantize(dev, q, scale, dst, stream)
     else:
         native.fp8_dequantize(dev, q, scale, dst, info["vpt"], stream)
+
+
+def gpu_region_decodable(info: Dict[str, Any]) -> bool:
+    """Whether ``dequantize_regions`` can decode a blob of this ``quant`` dict
+    region by region: the formats whose element ``i`` is decodable on its own
+    (``mx``, ``mxfp4``, ``mxfp6``, ``nvfp4``: its code and its scale byte sit at
+    offsets computed from ``i``).  The rotated formats (``hadamard32``,
+    ``mxfp4_hadamard32``) need whole groups of 32 through the matrix cores, and
+    the fp32-scale ``block`` layout was left on its kernels: those are restored
+    whole by ``dequantize_device``, or on the host."""
+    from . import native
+
+    return bool(info) and info.get("format") in native.DEQUANT_FORMATS \
+        and info.get("rotation", "none") == "none"
+
+
+def _whole_piece(entry: TensorEntry, narrows) -> bool:
+    return all(start == 0 and length == int(entry.shape[d]) for d, start, length in narrows or ())
+
+
+def dequantize_regions(blob_dev: torch.Tensor, entry: TensorEntry, regions, stream: int):
+    """GPU decode of boxes of a quantized blob in HBM into CUDA views, on
+    ``stream`` (a handle), which is not synchronized here: the caller does
+    that and holds the returned object (or None) until then.  ``regions``: list
+    of ``(narrows or None, dst_view)``, ``narrows`` a list of ``(dim, start,
+    length)`` on the entry's ``shape`` (the regions of
+    ``staging.scatter_host_regions``); ``dst_view`` has the box's shape, any
+    strides, and dtype bf16, f16 or f32 (it need not be the entry's: the decode
+    is fp32, then one rounding).  A single region that is the whole piece into
+    a contiguous view of the entry's dtype goes to the streaming kernels
+    (``dequantize_device``), everything else to ``hs_dequant_regions`` in one
+    launch; the entry must be ``gpu_region_decodable`` then."""
+    from . import native
+
+    info = entry.quant
+    if len(regions) == 1:
+        narrows, dst = regions[0]
+        if (_whole_piece(entry, narrows) and dst.is_contiguous()
+                and dst.dtype == string_to_dtype(entry.dtype)):
+            st = (torch.cuda.ExternalStream(stream, device=dst.device) if stream
+                  else torch.cuda.default_stream(dst.device))
+            with torch.cuda.stream(st):
+                dequantize_device(blob_dev, entry, dst)
+            return None
+    if not gpu_region_decodable(info):
+        raise ValueError(f"quantized format {info.get('format')!r} (rotation "
+                         f"{info.get('rotation')!r}) is not decodable by regions")
+    p, total = info["payload_bytes"], info["total_bytes"]
+    dev = regions[0][1].device.index or 0
+    amax = blob_dev[total - 4: total] if is_nvfp4(info) else None
+    return native.dequant_regions(dev, info["format"], blob_dev[:p],
+                                  blob_dev[p: p + info["nblocks"]], amax, entry.shape, regions,
+                                  stream, sync=False)

@@ -16,9 +16,15 @@ bytes of a quantize, destination bytes of a dequantize).
     fp8_kernels_bench.py [--dtype bf16|f32] [--offset] [--rounds R] [--mi-elems M] [mode ...]
 
 Modes: ``mx_e8m0``, ``none``, ``hadamard32``, ``mxfp4``, ``mxfp4_hadamard32``,
-``mxfp6``, ``nvfp4``, ``probe``, ``probe_mx``.  ``--rounds R`` goes
+``mxfp6``, ``nvfp4``, ``probe``, ``probe_mx``, ``regions`` (alone).  ``--rounds R`` goes
 through the list of modes R times, so that two modes alternate and the spread
 of one mode's repeats is seen beside the difference between the two.
+
+``regions`` measures ``hs_dequant_regions`` on an 8192 x 8192 piece in the four
+region-decodable formats: (a) the whole piece into a contiguous tensor beside
+the streaming dequantizer, (b) a row half and (c) a column half beside the
+two-pass of the existing entry points (stream-dequantize the whole piece into
+scratch, then one ``hs_copy_nd`` of the region).
 
 ``--offset`` shifts the source and the restored tensor by one element, so
 neither has the alignment of the vector loads and stores."""
@@ -53,6 +59,70 @@ def timeit(fn, iters=10):
     return min(ts), sorted(ts)[len(ts) // 2], min(es), sorted(es)[len(es) // 2]
 
 
+def regions_mode(dtype, rounds):
+    dev, side = 0, 8192
+    hs = int(torch.cuda.current_stream().cuda_stream)
+    w = torch.empty(side, side, dtype=dtype, device="cuda:0").normal_()
+    from hipsnapshot.format.manifest import TensorEntry
+    from hipsnapshot.format.serialization import SER, dtype_to_string
+
+    sets = {"whole": None, "rows": [(0, 0, side // 2)], "cols": [(1, 0, side // 2)]}
+    blobs = {}  # quantized once per format, by the kernels, in HBM
+    for fmt in ["mx", "mxfp4", "mxfp6", "nvfp4"]:
+        info = quant.fp8_entry_quant_info(w, fmt=fmt)
+        p, total = info["payload_bytes"], info["total_bytes"]
+        blob = torch.zeros(total, dtype=torch.uint8, device="cuda:0")
+        if fmt == "nvfp4":
+            native.nvfp4_quantize(dev, w, blob[:p], blob[p: total - 4], blob[total - 4:], hs)
+        else:
+            quantize = {"mx": native.mx8_quantize, "mxfp4": native.mxfp4_quantize,
+                        "mxfp6": native.mxfp6_quantize}[fmt]
+            quantize(dev, w, blob[:p], blob[p:], hs)
+        blobs[fmt] = (info, blob)
+    torch.cuda.synchronize()
+    for fmt in ["mx", "mxfp4", "mxfp6", "nvfp4"] * rounds:
+        info, blob = blobs[fmt]
+        entry = TensorEntry("w", SER.FP8_BLOCK, dtype_to_string(dtype), [side, side], False,
+                            quant=info)
+        p, total = info["payload_bytes"], info["total_bytes"]
+        am = blob[total - 4: total] if fmt == "nvfp4" else None
+        scratch = torch.empty_like(w)
+        for name, narrows in sets.items():
+            src = scratch
+            for d, start, length in narrows or ():
+                src = src.narrow(d, start, length)
+            dst = torch.empty(src.shape, dtype=dtype, device="cuda:0")
+
+            keep = []  # descriptor stages and workspaces, until timeit has synchronized
+
+            def kernel():
+                keep.append(native.dequant_regions(dev, info["format"], blob[:p],
+                                                   blob[p: p + info["nblocks"]], am, entry.shape,
+                                                   [(narrows, dst)], hs, sync=False))
+
+            def two_pass():
+                quant.dequantize_device(blob, entry, scratch)
+                if narrows is not None:
+                    batch = native.CopyBatch()
+                    native.tensor_copy_descriptor(batch, src, dst)
+                    batch.launch(dev, hs, sync=False)
+
+            results = {}
+            for what, fn in (("regions", kernel), ("streaming" if narrows is None else "two_pass",
+                                                  two_pass)):
+                dst.zero_()
+                best, med, ev_best, ev_med = timeit(fn)
+                results[what] = (scratch if what == "streaming" else dst).clone()
+                # the two paths' outputs at the timed size, bit for bit
+                same = all(torch.equal(r.view(torch.uint8), results["regions"].view(torch.uint8))
+                           for r in results.values())
+                print(json.dumps({"kernel": f"{what}_{name}_{fmt}", "dtype": str(dtype),
+                                  "same_bits_as_regions": same,
+                                  "ms_median": round(med * 1e3, 4),
+                                  "event_ms_best": round(ev_best * 1e3, 4),
+                                  "event_ms_median": round(ev_med * 1e3, 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
@@ -65,6 +135,8 @@ def main():
     torch.cuda.set_device(dev)
     modes = args.modes * args.rounds
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    if "regions" in args.modes:
+        return regions_mode(dtype, args.rounds)
     off = 1 if args.offset else 0
     nw = args.mi_elems << 20
     w = torch.empty(nw + off, dtype=dtype, device="cuda:0").normal_()[off:]
